@@ -13,17 +13,24 @@ value = ray segments (calculateRayCollision calls, computeShader.c:450) of all r
 max-over-ranks wall time, in Mrays/s.  Segment counts come from an untimed counting pass
 over the same frames (reference traversal semantics; identical image).
 
-The default run (C2 on one GPU) also times the global-memory configs C3 and C4 (2 steps each)
-and reports them under "secondary", each with its own roofline.
+A plain run does only what the headline figure needs: scene, warm-up, the timed steps, the
+counting pass, and the line.  --dump-outputs DIR then saves the image the last timed step
+left (DIR/image.npy, float32, with the few NaN words the reference's shading yields set to 0,
+and DIR/nonfinite.npy marking their pixels), so that two builds can be compared output for output: the
+scene, the frames and every pixel's RNG stream are fixed, so the same arguments give the same
+inputs on every run.
 
-Every line carries its own parity check (`parity`): after the timed region rank 0 renders
-sampled pixels of the timed image (frames 1..spp, the assembled frame at N > 1) with the CPU
-oracle (test infrastructure, never timed) and counts the words that differ; on one GPU the
-frames of the cpu_baseline sample are also re-rendered on the timed context and compared in
-full with the oracle image that leg computes.  --force-dist takes the N > 1 path (process
-group, scene broadcast, device row copy, all-gather) at world size 1.
+--full adds everything else the line can carry.  The cold first render.  For C2 on one GPU,
+the global-memory configs C3 and C4 (2 steps each) under "secondary", each with its own
+roofline.  The CPU baseline.  And the line's own parity check (`parity`): after the timed
+region rank 0 renders sampled pixels of the timed image (frames 1..spp, the assembled frame at
+N > 1) with the CPU oracle (test infrastructure, never timed) and counts the words that
+differ; on one GPU the frames of the cpu_baseline sample are also re-rendered on the timed
+context and compared in full with the oracle image that leg computes.  --force-dist takes the
+N > 1 path (process group, scene broadcast, device row copy, all-gather) at world size 1.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C4|C5]
+                       [--dump-outputs DIR] [--full]
 N>1:   python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -206,6 +213,42 @@ def roofline_from(pmc, stale, lib_sha, avg_launch_ms, n_launch, segments_per_lau
     return r
 
 
+DUMP_LIMIT = 64 << 20     # bytes --dump-outputs may write in all
+
+
+def dump_outputs(directory, arrays, seed=0x5EED):
+    """--dump-outputs: each array as <directory>/<name>.npy, float32 (float64 for anything
+    that is not float32), at most DUMP_LIMIT bytes in all.  When the arrays together are over
+    the limit, each is saved as a sample of its rows (last axis kept): the same fraction of
+    every array, drawn with a fixed seed and kept in order, so two runs with the same
+    arguments save the same rows, and arrays with the same number of rows the same ones."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(a, np.float32 if a.dtype == np.float32 else np.float64)
+              for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT:
+            rows = a.reshape(-1, a.shape[-1])
+            keep = len(rows) * DUMP_LIMIT // total
+            idx = np.sort(np.random.default_rng(seed).choice(len(rows), size=keep, replace=False))
+            a = rows[idx]
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
+def finite_outputs(img):
+    """The arrays --dump-outputs saves for an RGBA32F frame.  A frame may hold NaN: the
+    reference's shading yields a NaN sample now and then (6 pixels of C2's 1920x1080 image
+    after 1024 frames, the same pixels in the CPU oracle), and the running mean keeps it.  NaN
+    compares unequal to itself, so two builds could not be compared on such words: `image` is
+    the frame with every non-finite word set to 0, and `nonfinite` (H x W x 1) is 1 at the
+    pixels that held one, 0 elsewhere, so where they fell is compared too."""
+    import numpy as np
+    bad = ~np.isfinite(img)
+    return {"image": np.where(bad, np.float32(0), img),
+            "nonfinite": bad.any(axis=-1, keepdims=True).astype(np.float32)}
+
+
 def parity_pixels_for(spp, requested):
     """Pixels of the timed image checked against the oracle: about 16 M oracle pixel-frames
     (C2: 16384 pixels x 1024 frames, about 1.5 s on a 16-CPU share), 1024..16384."""
@@ -356,7 +399,8 @@ def measure(cfg, args, ctx, steps, warmup, cold=True, W=None, H=None, spp=None, 
         dt = float(t.item())
 
     # the image the timed steps produced (N > 1: the assembled frame; otherwise this
-    # context's rows, y = rank + k * world), kept for the parity check and --dump-frame
+    # context's rows, y = rank + k * world), kept for the parity check, --dump-frame and
+    # --dump-outputs
     timed_img = None
     if rank == 0 and (parity_pixels or dump):
         timed_img = img.cpu().numpy() if img is not None else pt.read_rgba32f()
@@ -446,7 +490,21 @@ def main():
     ap.add_argument("--force-dist", action="store_true",
                     help="take the N>1 path (process group, scene broadcast, device row copy, all-gather) "
                          "even at world size 1: a one-GPU rehearsal of the RCCL leg")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps rank 0 saves what the last one computed as DIR/<name>.npy "
+                         "(image.npy: the RGBA32F frame, non-finite words set to 0; nonfinite.npy: 1 at the "
+                         "pixels that held one; a fixed seeded sample of the pixels above 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the cold first "
+                         "render, the secondary configs, the CPU baseline and the parity checks against the "
+                         "CPU oracle (--no-cold, --secondary, --no-cpu-baseline and --parity-pixels choose "
+                         "among them)")
     args = ap.parse_args()
+    if not args.full:
+        if args.secondary not in (None, "none") or (args.parity_pixels or 0) > 0:
+            ap.error("--secondary and --parity-pixels need --full")
+        args.no_cold = args.no_cpu_baseline = True
+        args.secondary, args.parity_pixels = "none", 0
 
     import torch
 
@@ -485,10 +543,13 @@ def main():
     spp_head = args.spp or CONFIGS[args.config][3]
     want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
     m = measure(args.config, args, ctx, args.steps, args.warmup, cold=not args.no_cold, W=args.width,
-                H=args.height, spp=args.spp, bounces=args.bounces, chunk=args.chunk, dump=bool(args.dump_frame),
+                H=args.height, spp=args.spp, bounces=args.bounces, chunk=args.chunk,
+                dump=bool(args.dump_frame or args.dump_outputs),
                 parity_pixels=parity_pixels_for(spp_head, args.parity_pixels),
                 full_frames=args.cpu_spp if want_cpu and args.parity_pixels != 0 else 0)
     W, H, spp, bounces, scene = m["W"], m["H"], m["spp"], m["bounces"], m["scene"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, finite_outputs(m["frame"]))
 
     sec_cfgs = []
     if args.secondary is None:

@@ -9,12 +9,30 @@ for p in (os.path.join(REPO, "tests"), PKG):
     if p not in sys.path:
         sys.path.insert(0, p)
 
-REF_SCENES = "/root/reference/LearnOpenGL/scene_data"
+REF_SCENES_GZ = os.path.join(REPO, "tests", "golden", "scene_data")
+
+
+def unpack_ref_scenes(dest):
+    """The reference's shipped scenes (scene_data/{ship,p,p2,drift}{obj,mtl}.txt), stored
+    gzip-compressed under tests/golden/scene_data, written out as text files in `dest`."""
+    import gzip
+    for name in sorted(os.listdir(REF_SCENES_GZ)):
+        if name.endswith(".txt.gz"):
+            with gzip.open(os.path.join(REF_SCENES_GZ, name), "rb") as src, \
+                    open(os.path.join(dest, name[:-3]), "wb") as dst:
+                dst.write(src.read())
+    return dest
 
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs an MI355X (runs the HIP kernels)")
     config.addinivalue_line("markers", "slow: long-running CPU check")
+
+
+@pytest.fixture(scope="session")
+def ref_scenes(tmp_path_factory):
+    """Directory holding the reference's shipped scene files, unpacked once per session."""
+    return unpack_ref_scenes(str(tmp_path_factory.mktemp("scene_data")))
 
 
 @pytest.fixture(scope="session")

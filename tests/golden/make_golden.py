@@ -1,9 +1,9 @@
 """Regenerates the committed fixtures in tests/golden/ (run in the dev container).
 
 ship_scene.npz     : the reference's scene_data/ship{obj,mtl}.txt as loaded by the product
-                     loader (pt_scene_load_obj) -- loader parity vs the oracle's istream
-                     restatement is tested on CPU where /root/reference exists; the GPU box
-                     has no /root/reference, so the loaded arrays travel as data.
+                     loader (pt_scene_load_obj) from the texts stored under scene_data/ --
+                     loader parity vs the oracle's istream restatement is tested on CPU; the
+                     loaded arrays travel as data for the GPU tests.
 ref_scenes.npz     : the reference's scene_data/drift*, p* and p2* scenes (11,846 / 6,258 / 6,258
                      triangles, the inputs that take the global-memory walk), loaded the same way
                      and checked against the oracle's loader; keys <scene>_tris / <scene>_mats.
@@ -15,18 +15,20 @@ golden_images.npz  : small RGBA32F renders, each produced by the C++ oracle AND 
 import os
 import sys
 
+import tempfile
+
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 sys.path[:0] = [os.path.join(REPO, "tests"), os.path.join(REPO, "oracle"), os.path.join(REPO, "opengl-path-tracing_amd")]
 
+import conftest  # noqa: E402
 import numpy_twin  # noqa: E402
 import oracle_lib  # noqa: E402
 import pt_host  # noqa: E402
 import pt_scenes  # noqa: E402
 
-REF = "/root/reference/LearnOpenGL/scene_data"
 
 CASES = [
     ("cornell", 64, 48, 5, 1, 1), ("cornell", 64, 48, 5, 1, 4), ("cornell", 64, 48, 8, 1, 16),
@@ -36,7 +38,8 @@ CASES = [
 
 
 def main(part="all"):
-    if os.path.isdir(REF) and part in ("all", "ref"):
+    if part in ("all", "ref"):
+        REF = conftest.unpack_ref_scenes(tempfile.mkdtemp(prefix="scene_data"))
         t, m = pt_host.load_vertex_data(os.path.join(REF, "shipobj.txt"), os.path.join(REF, "shipmtl.txt"))
         to, mo = oracle_lib.load_obj(os.path.join(REF, "shipobj.txt"), os.path.join(REF, "shipmtl.txt"))
         assert np.array_equal(t.view(np.uint32), to.view(np.uint32)) and np.array_equal(m.view(np.uint32), mo.view(np.uint32))

@@ -173,3 +173,44 @@ def test_bench_timed_image_parity_check(cornell_scene):
     assert r["mismatches"] == 200
     assert bench.parity_pixels_for(1024, None) == 16384 and bench.parity_pixels_for(4096, None) == 4096
     assert bench.parity_pixels_for(256, 0) == 0
+
+
+def test_bench_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): arrays under the limit are saved whole, float32 as
+    float32 and anything else as float64; over it, as a seeded sample of their rows that fits,
+    the same rows on every call.  bench.finite_outputs: every saved value of a frame is finite,
+    a non-finite word is saved as 0 and its pixel marked in `nonfinite`, also in a sample."""
+    import numpy as np
+    import bench
+    assert bench.DUMP_LIMIT == 64 << 20
+    rng = np.random.default_rng(3)
+    img = rng.random((9, 7, 4), dtype=np.float32)
+    img[..., 3] = np.arange(63, dtype=np.float32).reshape(9, 7)      # the pixel's own index
+    bench.dump_outputs(str(tmp_path / "a"), {"image": img, "count": np.arange(5, dtype=np.int64)})
+    got = np.load(tmp_path / "a" / "image.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, img)
+    cnt = np.load(tmp_path / "a" / "count.npy")
+    assert cnt.dtype == np.float64 and np.array_equal(cnt, np.arange(5))
+    bad = img.copy()
+    bad[2, 3, 0], bad[2, 3, 2], bad[8, 6, 1], bad[0, 0, 0] = np.nan, -np.nan, np.inf, -np.inf
+    out = bench.finite_outputs(bad)
+    assert sorted(out) == ["image", "nonfinite"] and all(np.isfinite(a).all() for a in out.values())
+    assert out["image"].dtype == np.float32 and out["nonfinite"].shape == (9, 7, 1)
+    hit = np.zeros((9, 7), bool)
+    hit[2, 3] = hit[8, 6] = hit[0, 0] = True
+    assert np.array_equal(out["nonfinite"][..., 0], hit.astype(np.float32))
+    assert np.array_equal(out["image"][~np.isfinite(bad)], np.zeros(4, np.float32))
+    assert np.array_equal(out["image"][np.isfinite(bad)], img[np.isfinite(bad)])
+    clean = bench.finite_outputs(img)
+    assert np.array_equal(clean["image"], img) and not clean["nonfinite"].any()
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 20 * 20)       # room for 20 pixels and their marks
+    bench.dump_outputs(str(tmp_path / "b"), out)
+    bench.dump_outputs(str(tmp_path / "c"), out)
+    b, c = np.load(tmp_path / "b" / "image.npy"), np.load(tmp_path / "c" / "image.npy")
+    mark = np.load(tmp_path / "b" / "nonfinite.npy")
+    assert b.shape == (20, 4) and b.dtype == np.float32 and mark.shape == (20, 1) and np.array_equal(b, c)
+    assert b.nbytes + mark.nbytes <= 20 * 20
+    idx = b[:, 3].astype(int)                               # which pixels the sample kept, in order
+    assert len(set(idx)) == 20 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(b, out["image"].reshape(-1, 4)[idx])
+    assert np.array_equal(mark[:, 0], hit.reshape(-1)[idx].astype(np.float32))

@@ -36,7 +36,7 @@ def test_bench_ranks_gloo_one_gpu(tmp_path, cornell_scene, world, config):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", str(world),
            "--config", config, "--dist-backend", "gloo", "--width", str(W), "--height", str(Hh), "--spp", str(spp),
-           "--chunk", str(chunk), "--steps", "1", "--warmup", "1", "--no-cold", "--no-cpu-baseline",
+           "--chunk", str(chunk), "--steps", "1", "--warmup", "1", "--full", "--no-cold", "--no-cpu-baseline",
            "--dump-frame", out]
     tj = None
     if world == 2:
@@ -82,8 +82,8 @@ def test_bench_share_proxy_line(tmp_path):
     W, Hh, spp = 96, 40, 4
     out = str(tmp_path / "frame.npy")
     cmd = [sys.executable, "bench.py", "--config", "C2", "--share-of", "4", "--width", str(W), "--height", str(Hh),
-           "--spp", str(spp), "--chunk", "2", "--steps", "1", "--warmup", "1", "--no-cold", "--no-cpu-baseline",
-           "--dump-frame", out]
+           "--spp", str(spp), "--chunk", "2", "--steps", "1", "--warmup", "1", "--full", "--no-cold",
+           "--no-cpu-baseline", "--dump-frame", out]
     r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -113,7 +113,7 @@ def test_bench_rccl_leg_world_one(tmp_path, cornell_scene, config):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "1",
            "--config", config, "--dist-backend", "nccl", "--force-dist", "--width", str(W), "--height", str(Hh),
-           "--spp", str(spp), "--chunk", str(chunk), "--steps", "2", "--warmup", "1", "--no-cold",
+           "--spp", str(spp), "--chunk", str(chunk), "--steps", "2", "--warmup", "1", "--full", "--no-cold",
            "--no-cpu-baseline", "--parity-pixels", "300", "--dump-frame", out]
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=420)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -132,3 +132,34 @@ def test_bench_rccl_leg_world_one(tmp_path, cornell_scene, config):
     pt.close()
     assert img.shape == want.shape
     assert_bitwise(img, want, "RCCL world-1 bench frame vs one context")
+
+
+def test_bench_plain_run_dumps_its_image(tmp_path, cornell_scene):
+    """A plain bench.py run (no --full) times the headline only -- no cold render, secondary
+    config, CPU baseline or oracle check in its line -- and --dump-outputs saves the image its
+    last timed step left, bit for bit one context's render of the same frames, every value
+    finite (a non-finite word as 0, its pixel marked in nonfinite.npy)."""
+    import json
+    W, Hh, spp = 96, 40, 4
+    out = tmp_path / "dump"
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--width", str(W),
+           "--height", str(Hh), "--spp", str(spp), "--chunk", "2", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["unit"] == "Mrays/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["cold_ms_per_step"] is None and line["cpu_baseline"] is None and line["parity"] is None
+    assert line["secondary"] == []
+    assert sorted(os.listdir(out)) == ["image.npy", "nonfinite.npy"]
+    img, mark = np.load(out / "image.npy"), np.load(out / "nonfinite.npy")
+    assert img.dtype == np.float32 and mark.dtype == np.float32 and mark.shape == (Hh, W, 1)
+    assert np.isfinite(img).all() and np.isfinite(mark).all()
+    pt = H.PathTracer(W, Hh, max_bounce=8)
+    pt.upload(cornell_scene)
+    pt.render(1, spp, 0)
+    want = pt.read_rgba32f()
+    pt.close()
+    bad = ~np.isfinite(want)                     # saved as 0, their pixels marked
+    assert np.array_equal(mark[..., 0], bad.any(-1).astype(np.float32))
+    assert_bitwise(img, np.where(bad, np.float32(0), want), "plain bench dump vs one context")

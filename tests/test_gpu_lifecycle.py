@@ -97,7 +97,7 @@ def _device_count():
     return torch.cuda.device_count()
 
 
-@pytest.mark.skipif("_device_count() < 2")
+@pytest.mark.skipif("_device_count() < 2", reason="needs two GPUs")
 def test_two_devices_one_process(cornell_scene):
     """Contexts on devices 0 and 1 driven alternately from one thread: every entry point
     selects its context's device (sync, readback, ACES, tuning)."""

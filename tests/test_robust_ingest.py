@@ -14,7 +14,6 @@ import pytest
 
 import pt_host as H
 import pt_scenes
-from conftest import REF_SCENES
 
 
 def bits(a):
@@ -29,10 +28,9 @@ def test_robust_equals_reference_loader(name, tmp_path):
     assert np.array_equal(bits(t_ref), bits(t_rob)) and np.array_equal(bits(m_ref), bits(m_rob))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_SCENES), reason="reference scene_data not mounted")
 @pytest.mark.parametrize("name", ["ship", "p", "p2", "drift"])
-def test_robust_equals_reference_loader_on_shipped_scenes(name):
-    obj, mtl = os.path.join(REF_SCENES, name + "obj.txt"), os.path.join(REF_SCENES, name + "mtl.txt")
+def test_robust_equals_reference_loader_on_shipped_scenes(name, ref_scenes):
+    obj, mtl = os.path.join(ref_scenes, name + "obj.txt"), os.path.join(ref_scenes, name + "mtl.txt")
     t_ref, m_ref = H.load_vertex_data(obj, mtl)
     t_rob, m_rob = H.load_obj_robust(obj, mtl)
     assert np.array_equal(bits(t_ref), bits(t_rob)) and np.array_equal(bits(m_ref), bits(m_rob))

@@ -3,7 +3,7 @@
 tests/sanitize/host_fuzz.cpp links csrc/pt_scene.cpp and csrc/pt_viewer.cpp with
 -fsanitize=address,undefined -fno-sanitize-recover=all and drives:
   * both loaders (reference semantics, geometry_loader.h:15-142, and the robust reader) on the
-    generated Cornell scene, the reference's shipped scenes when mounted, and a few thousand
+    generated Cornell scene, the reference's shipped scenes (tests/golden/scene_data), and a few thousand
     mutated OBJ/MTL texts (byte flips, truncation, long lines, huge / negative indices, NaN);
   * the SAH builder (bvh.h:173-268) on every accepted scene, twice (scene object and raw
     arrays, which must agree), and an undersized node buffer, which must be refused;
@@ -15,8 +15,6 @@ import os
 import subprocess
 
 import pytest
-
-from conftest import REF_SCENES
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SAN = os.path.join(REPO, "tests", "sanitize")
@@ -30,14 +28,12 @@ def host_fuzz(tmp_path_factory):
     return os.path.join(out, "host_fuzz")
 
 
-def test_host_ingest_under_asan_ubsan(host_fuzz, cornell_paths, tmp_path):
+def test_host_ingest_under_asan_ubsan(host_fuzz, cornell_paths, ref_scenes, tmp_path):
     import pt_scenes
     args = list(cornell_paths)
     args += list(pt_scenes.write_scene("bunny", str(tmp_path), target_tris=2000))
     for name in ("ship", "p", "drift"):
-        obj, mtl = os.path.join(REF_SCENES, name + "obj.txt"), os.path.join(REF_SCENES, name + "mtl.txt")
-        if os.path.exists(obj) and os.path.exists(mtl):
-            args += [obj, mtl]
+        args += [os.path.join(ref_scenes, name + "obj.txt"), os.path.join(ref_scenes, name + "mtl.txt")]
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
                UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     r = subprocess.run([host_fuzz, str(tmp_path), "3000"] + args, capture_output=True, text=True,

@@ -2,7 +2,7 @@
 
 Reference: geometry_loader.h:15-142 (load_vertex_data), bvh.h:84-268 (buildSAHTree,
 find_split, build_links), ogl_path_trace.h:415-507 (built-ins).  Bit-exact on every array.
-The reference's own scene files are used when /root/reference is mounted (dev container).
+The reference's own scene files travel as fixtures (tests/golden/scene_data, conftest.ref_scenes).
 """
 import os
 
@@ -12,7 +12,6 @@ import pytest
 import oracle_lib as O
 import pt_host as H
 import pt_scenes
-from conftest import REF_SCENES
 
 SHIPPED = {"ship": (2520, 6), "p": (6258, 11), "p2": (6258, 11), "drift": (11846, 24)}
 
@@ -25,23 +24,18 @@ def same(a, b):
     return a.shape == b.shape and np.array_equal(bits(a), bits(b))
 
 
-needs_ref = pytest.mark.skipif(not os.path.isdir(REF_SCENES), reason="reference scene_data not mounted")
-
-
-@needs_ref
 @pytest.mark.parametrize("name", sorted(SHIPPED))
-def test_loader_matches_oracle_on_reference_scenes(name):
-    obj, mtl = os.path.join(REF_SCENES, name + "obj.txt"), os.path.join(REF_SCENES, name + "mtl.txt")
+def test_loader_matches_oracle_on_reference_scenes(name, ref_scenes):
+    obj, mtl = os.path.join(ref_scenes, name + "obj.txt"), os.path.join(ref_scenes, name + "mtl.txt")
     tp, mp = H.load_vertex_data(obj, mtl)
     to, mo = O.load_obj(obj, mtl)
     assert (len(tp), len(mp)) == SHIPPED[name]
     assert same(tp, to) and same(mp, mo)
 
 
-@needs_ref
 @pytest.mark.parametrize("name", ["ship", "p", "p2"])
-def test_bvh_matches_oracle_on_reference_scenes(name):
-    tp, _ = H.load_vertex_data(os.path.join(REF_SCENES, name + "obj.txt"), os.path.join(REF_SCENES, name + "mtl.txt"))
+def test_bvh_matches_oracle_on_reference_scenes(name, ref_scenes):
+    tp, _ = H.load_vertex_data(os.path.join(ref_scenes, name + "obj.txt"), os.path.join(ref_scenes, name + "mtl.txt"))
     assert same(H.buildSAHTree(tp), O.build_bvh(tp))
 
 

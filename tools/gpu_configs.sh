@@ -7,7 +7,7 @@
 cd "$GRAFT_REPO_ROOT"; O="$GRAFT_REPO_ROOT/gpurun_out/cfg"; mkdir -p "$O"
 run() {  # name args...
   local name=$1; shift
-  timeout -k 10 600 python bench.py --no-cpu-baseline --no-cold --secondary none "$@" > "$O/$name.json" 2> "$O/$name.err" || return $?
+  timeout -k 10 600 python bench.py --full --no-cpu-baseline --no-cold --secondary none "$@" > "$O/$name.json" 2> "$O/$name.err" || return $?
   echo "$name $(python3 -c "import json;d=json.load(open('$O/$name.json'));print(d['value'],d['ms_per_frame'])")"
 }
 for c in ${CONFIGS:-C2 C3 C4 C5}; do run $c --config $c || exit $?; done

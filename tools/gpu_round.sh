@@ -23,11 +23,11 @@ for w in $PMC_WORLDS; do
   python3 tools/pmc_traffic.py "$O/pmc/C2_w$w" "$TAG" C2 world=$w > "$O/pmc_summary_C2_w$w.json" || exit 1
 done
 cp profiles/pmc/*.json "$O/profiles/pmc/"; cp profiles/${TAG}_pmc_*.json "$O/profiles/" 2>/dev/null
-timeout -k 10 900 python bench.py > "$O/round_bench.json" 2> "$O/round_bench.err"; rc=$?
+timeout -k 10 900 python bench.py --full > "$O/round_bench.json" 2> "$O/round_bench.err"; rc=$?
 echo "bench rc=$rc"; cat "$O/round_bench.json"
 [ $rc -eq 0 ] || exit $rc
 cd /tmp
 timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/round_kt" -o run -- \
-    python3 "$R/bench.py" --no-cpu-baseline > "$O/round_kt_bench.json" 2> "$O/round_kt.err"; rc=$?
+    python3 "$R/bench.py" --full --no-cpu-baseline > "$O/round_kt_bench.json" 2> "$O/round_kt.err"; rc=$?
 echo "rocprof kt rc=$rc"; cat "$O/round_kt_bench.json"
 exit $rc
