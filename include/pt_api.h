@@ -164,7 +164,9 @@ int pt_set_kernel(pt_ctx* ctx, int variant);
  *         several lanes and the running mean is applied by a second kernel in frame order;
  *         a value >= n_frames gives each lane whole pixels (running mean in registers).
  *         In automatic mode launches of at most 16 frames always take the split path (its
- *         batched queue reservations), whatever their group.
+ *         batched queue reservations), whatever their group.  While the moments are on
+ *         (pt_set_moments) every launch takes the split path, since the accumulate pass keeps
+ *         them: a value >= n_frames then means one item per pixel, still split.
  * key 6 = walk floor (1..64, 0 = auto): a walk phase ends once fewer lanes than this still
  *         walk, and the leaf (or shading) phase runs even below its threshold.
  * key 7 = leaf-phase compaction limit (0..63, default 63): the edge tests of a wave's leaf
@@ -197,6 +199,55 @@ int pt_set_kernel(pt_ctx* ctx, int variant);
  *         drops a captured graph.
  * None of these change the image (each pixel's frames stay in order in one lane). */
 int pt_set_tuning(pt_ctx* ctx, int key, int value);
+
+/* Per-pixel noise estimate and render-until-converged.
+ *
+ * With moments on, the accumulate pass keeps two sums per local pixel beside the image: for
+ * each frame's colour c, in frame order, as separately rounded binary32 operations,
+ *   Y = (c.x*0.2126f + c.y*0.7152f) + c.z*0.0722f;   S1 = S1 + Y;   S2 = S2 + Y*Y;
+ * They restart from (0, 0) whenever the image does (a render with accumulate = 0, frame 1 of
+ * a progressive run) and continue otherwise; pixels outside the dispatch footprint
+ * (PT_FLAG_REF_DISPATCH) are never touched.  `frames` is the number n of frames folded in
+ * since that restart.  The relative error of a pixel after n >= 2 frames, nf = (float)n:
+ *   m = S1/nf;  v = max(S2/nf - m*m, 0);  sem = sqrt(v/(float)(n-1));  rel = sem/(m + 0.01f);
+ *   rel = 64 unless 0 <= rel <= 64 (NaN or infinite moments included);
+ *   q = (unsigned)(rel * 65536.0f)                   (truncated; q <= 2^22)
+ * The summary holds integers only, so it does not depend on the order of the reduction and
+ * adds exactly across the contexts of a split image (pt_group_noise). */
+typedef struct {
+    unsigned long long pixels;   /* footprint pixels of the local rows */
+    unsigned long long sum_q;    /* sum of q  (mean rel = sum_q / pixels / 65536) */
+    unsigned long long above;    /* pixels with q > (unsigned)(target * 65536.0f) */
+    unsigned int max_q;
+    int frames;                  /* n */
+} pt_noise_stats;
+
+/* Turns the moments on (allocated and zeroed) or off (freed); frames = 0 either way.  While
+ * they are on every launch runs in frame-split mode (tuning key 5); the image is the same
+ * with them on or off.  A change drains the context's streams and drops a captured graph.
+ * pt_write_rgba32f, pt_set_camera and pt_upload_scene leave the moments alone: the caller's
+ * next restarting render clears them, as it does the image. */
+int pt_set_moments(pt_ctx* ctx, int enable);
+/* The local rows' moments, rows_local * width * 2 floats (S1, S2 per pixel, pixel order of
+ * pt_read_rgba32f), and the frames in them.  PT_E_STATE: moments off. */
+int pt_read_moments(pt_ctx* ctx, float* host_dst, size_t bytes, int* frames);
+/* The summary of the local rows, reduced on the device.  PT_E_STATE: moments off or fewer
+ * than 2 frames. */
+int pt_noise(pt_ctx* ctx, float target, pt_noise_stats* out);
+/* The same summary on the host, of n_pixels moment pairs; in_footprint (may be NULL = all)
+ * holds one byte per pixel, 0 = outside the footprint.  No device is touched: the per-pixel
+ * function is the device kernel's own code.  PT_E_ARG: frames < 2 or a null pointer. */
+int pt_noise_host(const float* moments, const unsigned char* in_footprint, size_t n_pixels, int frames,
+                  float target, pt_noise_stats* out);
+/* Renders frames frame_first, frame_first + 1, ... `batch` at a time (the first batch with
+ * the caller's accumulate flag, the rest accumulating) and stops after the first batch whose
+ * mean relative error is at or below `target`, sum_q <= (unsigned)(target * 65536.0f) *
+ * pixels, or after max_frames frames (the last batch may be shorter).  Turns the moments on
+ * if they are off.  Synchronous: one host round trip per batch.  The image afterwards is
+ * that of pt_render(frame_first, *frames_done, accumulate_first), bit for bit; `last` (may be
+ * NULL) receives the final summary.  PT_E_ARG: batch < 2, max_frames < batch or target <= 0. */
+int pt_render_until(pt_ctx* ctx, int frame_first, int accumulate_first, int batch, int max_frames,
+                    float target, int* frames_done, pt_noise_stats* last);
 
 #ifdef __cplusplus
 }

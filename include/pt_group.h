@@ -69,6 +69,11 @@ int pt_group_present_end(pt_group* g, int buf, const unsigned char** pixels);
  * root device, HIP events) and the bytes each device sent. */
 int pt_group_stats(const pt_group* g, double* gather_ms, size_t* bytes_per_device);
 
+/* The noise summary of the whole image (pt_api.h: pt_noise on every context): the integer
+ * fields added, max_q the largest.  PT_E_STATE: the contexts' frame counts differ (or a
+ * context has its moments off or fewer than 2 frames). */
+int pt_group_noise(pt_group* g, float target, pt_noise_stats* out);
+
 /* One-shot form: create a group, gather, destroy (sets up a communicator on every call). */
 int pt_gather_rgba32f(pt_ctx* const* ctxs, int n, float* dst, size_t bytes, int dst_on_device);
 

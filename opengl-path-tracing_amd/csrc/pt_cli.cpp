@@ -48,7 +48,12 @@ static void usage() {
                  "                  camera's 6 floats, then W*H*4 floats)\n"
                  "  --resume F      continue a saved accumulation: frames next_frame.. with accumulate = 1,\n"
                  "                  the same image as one uninterrupted run\n"
-                 "  --json          print a JSON summary line\n"
+                 "  --noise-target X  render until the mean per-pixel relative error (standard error of the\n"
+                 "                  mean luminance over the mean, pt_api.h: pt_render_until) is at most X,\n"
+                 "                  checked every --batch B frames (default 16), at most --max-spp N frames\n"
+                 "                  (default --spp); one GPU, not with --resume or --events\n"
+                 "  --json          print a JSON summary line (with --noise-target also frames_done,\n"
+                 "                  noise_mean, noise_max, noise_above_frac)\n"
                  "  --gpu-bvh       build the BVH on GPU 0 (pt_bvh_build_gpu; the same nodes)\n");
 }
 
@@ -173,6 +178,9 @@ int main(int argc, char** argv) {
     bool robust = false, json = false, gpu_bvh = false;
     const char* events = nullptr;
     std::string checkpoint, resume;
+    float noise_target = 0.0f;            // > 0: render until converged (pt_render_until)
+    int batch = 16, max_spp = 0;
+    bool until = false;
     for (int i = 3; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&](void) -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
@@ -191,6 +199,9 @@ int main(int argc, char** argv) {
         else if (a == "--events") events = next();
         else if (a == "--checkpoint") checkpoint = next();
         else if (a == "--resume") resume = next();
+        else if (a == "--noise-target") { noise_target = (float)std::atof(next()); until = true; }
+        else if (a == "--batch") batch = std::atoi(next());
+        else if (a == "--max-spp") max_spp = std::atoi(next());
         else if (a == "--json") json = true;
         else if (a == "--gpu-bvh") gpu_bvh = true;
         else { usage(); return 2; }
@@ -200,6 +211,19 @@ int main(int argc, char** argv) {
     if (events && (!resume.empty() || !checkpoint.empty())) {
         std::fprintf(stderr, "--events excludes --resume / --checkpoint\n");
         return 2;
+    }
+    if (until) {
+        // one context only: pt_render_until is not defined across a group, the moments are not
+        // part of a checkpoint, and an event script resets the image on its own schedule
+        if (gpus > 1 || ranks > 1 || !resume.empty() || events) {
+            std::fprintf(stderr, "--noise-target excludes --gpus / --ranks above 1, --resume and --events\n");
+            return 2;
+        }
+        if (max_spp == 0) max_spp = spp;
+        if (!(noise_target > 0.0f) || batch < 2 || max_spp < batch) {
+            std::fprintf(stderr, "--noise-target needs a target > 0, --batch >= 2 and --max-spp >= --batch\n");
+            return 2;
+        }
     }
     int first = 1;                        // frame number of the first frame rendered
     std::vector<float> prior;
@@ -267,6 +291,7 @@ int main(int argc, char** argv) {
     }
     auto t1 = std::chrono::steady_clock::now();
     int frames_run = 0, resets = 0;
+    pt_noise_stats noise = {0, 0, 0, 0, 0};
     if (events) {
         // the reference's render loop (ogl_path_trace.h:160-204) driven by a recorded session
         std::vector<Event> ev;
@@ -292,6 +317,11 @@ int main(int argc, char** argv) {
         }
         pt_viewer_destroy(view);
         spp = frames_run;
+    } else if (until) {
+        // frames 1.. in batches until the noise summary meets the target (or max_spp frames)
+        int done = 0;
+        CHECK(pt_render_until(ctx[0], 1, 0, batch, max_spp, noise_target, &done, &noise), ctx[0]);
+        spp = done;
     } else {
         for (int k = 0; k < spp; k += chunk) {
             const int n = std::min(chunk, spp - k), f0 = first + k;
@@ -335,12 +365,22 @@ int main(int argc, char** argv) {
             return 1;
         }
     }
-    if (json)
+    const double npx = noise.pixels ? (double)noise.pixels : 1.0;
+    if (until)
+        std::printf("noise target %g: %d frames, mean relative error %.5f, max %.5f, %.2f%% of pixels above\n",
+                    noise_target, spp, (double)noise.sum_q / npx / 65536.0, noise.max_q / 65536.0,
+                    100.0 * (double)noise.above / npx);
+    if (json) {
         std::printf("{\"width\": %d, \"height\": %d, \"frames\": %d, \"first_frame\": %d, \"bounces\": %d, "
                     "\"gpus\": %d, \"contexts\": %d, \"seconds\": %.6f, \"ms_per_frame\": %.4f, \"triangles\": %d, "
-                    "\"nodes\": %d, \"gather_ms\": %.4f}\n",
+                    "\"nodes\": %d, \"gather_ms\": %.4f",
                     W, H, spp, first, bounces, gpus, nctx, secs, secs * 1e3 / (spp > 0 ? spp : 1), cnt[0], cnt[3],
                     gather_ms);
+        if (until)
+            std::printf(", \"frames_done\": %d, \"noise_mean\": %.8f, \"noise_max\": %.8f, \"noise_above_frac\": %.8f",
+                        spp, (double)noise.sum_q / npx / 65536.0, noise.max_q / 65536.0, (double)noise.above / npx);
+        std::printf("}\n");
+    }
 
     if (FILE* f = std::fopen(pfm.c_str(), "wb")) {       // PFM rows run bottom-to-top: no flip
         std::fprintf(f, "PF\n%d %d\n-1.0\n", W, H);

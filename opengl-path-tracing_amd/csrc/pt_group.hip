@@ -416,6 +416,24 @@ int pt_group_stats(const pt_group* g, double* gather_ms, size_t* bytes_per_devic
     return PT_OK;
 }
 
+int pt_group_noise(pt_group* g, float target, pt_noise_stats* out) {
+    if (!g || !out) return PT_E_ARG;
+    pt_noise_stats sum = {0, 0, 0, 0, 0};
+    for (size_t i = 0; i < g->ctx.size(); i++) {
+        pt_noise_stats s;
+        const int rc = pt_noise(g->ctx[i], target, &s);
+        if (rc) return gfail(g, rc, std::string("pt_noise: ") + pt_last_error(g->ctx[i]));
+        if (i && s.frames != sum.frames) return gfail(g, PT_E_STATE, "the contexts' frame counts differ");
+        sum.frames = s.frames;
+        sum.pixels += s.pixels;      // integers: exact in any order
+        sum.sum_q += s.sum_q;
+        sum.above += s.above;
+        sum.max_q = s.max_q > sum.max_q ? s.max_q : sum.max_q;
+    }
+    *out = sum;
+    return PT_OK;
+}
+
 int pt_gather_rgba32f(pt_ctx* const* ctxs, int n, float* dst, size_t bytes, int dst_on_device) {
     pt_group* g = nullptr;
     int rc = pt_group_create(ctxs, n, &g);

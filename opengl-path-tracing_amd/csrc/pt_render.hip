@@ -21,6 +21,7 @@
 //   mat   48 B : {color.rgb, smoothness}, {emission*strength, specProb}, {specular.rgb, 0}
 //   sphere 32 B: {c.xyz, r*r}, {matIdx, 0, 0, 0}
 #include "pt_math.h"
+#include "pt_noise.h"
 #include "pt_wide.h"
 #include "../../include/pt_api.h"
 #include "../../include/pt_scene.h"
@@ -98,6 +99,7 @@ struct KParams {
     int wide_top;                  // wide walk (WIDE instantiations): records [0, wide_top) staged in LDS
     float wide_cw[3];              // ... 2^-18 * the scene's largest |coordinate| per axis, rounded up (WRay)
     int leaf_cert;                 // culling / wide walk: skip the exact leaf re-test where the hit certifies it
+    float2* moments;               // k_accum_frames<.., true>: luminance moments (S1, S2) beside accum (pt_noise.h)
 };
 
 // Progressive mode (hipGraph replay): the frame range comes from a device counter, and
@@ -1351,7 +1353,11 @@ constexpr int kAccumPix = PT_ACCUM_PIX;
 // against one frame per group, +1.1% with 4 x 4; the full 1080p image unchanged).  Short
 // launches keep 4 pixels and one frame per group (the pass beside the next one-frame render).
 constexpr int kAccumPixLong = 2, kAccumFramesLong = 8;
-template <int kAccumPix, int kAccumFrames>
+// MOMENTS: the per-frame luminance moments of the noise estimate (pt_noise.h) are kept beside
+// the image -- loaded with it (or zero where it restarts), updated after each frame's
+// accumulate() in the same frame order, stored with it.  The colours are already in registers
+// here, in frame order, in a pass that streams: 8 B more read and written per pixel per launch.
+template <int kAccumPix, int kAccumFrames, bool MOMENTS = false>
 __global__ __launch_bounds__(256) void k_accum_frames(KParams p) {
     resolve_frames(p);
     // the render that used these queue heads has ended (this pass runs after it): ready them
@@ -1364,6 +1370,7 @@ __global__ __launch_bounds__(256) void k_accum_frames(KParams p) {
     unsigned idx[kAccumPix];
     bool on[kAccumPix];
     float4 acc[kAccumPix];
+    float2 mom[MOMENTS ? kAccumPix : 1];
 #pragma unroll
     for (int j = 0; j < kAccumPix; j++) {
         idx[j] = base + (unsigned)j * blockDim.x;
@@ -1373,6 +1380,7 @@ __global__ __launch_bounds__(256) void k_accum_frames(KParams p) {
             on[j] = cx < p.x_limit && p.row0 + crow * p.row_stride < p.y_limit;
         }
         acc[j] = (on[j] && p.acc_first) ? p.accum[idx[j]] : make_float4(0, 0, 0, 0);
+        if constexpr (MOMENTS) mom[j] = (on[j] && p.acc_first) ? p.moments[idx[j]] : make_float2(0, 0);
     }
     // frames in groups of kAccumFrames whose loads are issued together, then applied in frame
     // order: one load group in flight per thread made a long launch's pass latency-bound when
@@ -1388,8 +1396,10 @@ __global__ __launch_bounds__(256) void k_accum_frames(KParams p) {
 #pragma unroll
         for (int u = 0; u < kAccumFrames; u++)
 #pragma unroll
-            for (int j = 0; j < kAccumPix; j++)
+            for (int j = 0; j < kAccumPix; j++) {
                 acc[j] = accumulate(acc[j], v[u][j], p.frame_first + k + u, k + u > 0 || p.acc_first == 1);
+                if constexpr (MOMENTS) ptn::add_sample(mom[j].x, mom[j].y, ptn::luminance(v[u][j].x, v[u][j].y, v[u][j].z));
+            }
     }
     for (; k < p.n_frames; k++) {
         f3 v[kAccumPix];
@@ -1397,12 +1407,17 @@ __global__ __launch_bounds__(256) void k_accum_frames(KParams p) {
         for (int j = 0; j < kAccumPix; j++)
             v[j] = on[j] ? nt_load3(p.rgb + 3 * ((size_t)k * (size_t)n + (size_t)idx[j])) : mk(0, 0, 0);
 #pragma unroll
-        for (int j = 0; j < kAccumPix; j++)
+        for (int j = 0; j < kAccumPix; j++) {
             acc[j] = accumulate(acc[j], v[j], p.frame_first + k, k > 0 || p.acc_first == 1);
+            if constexpr (MOMENTS) ptn::add_sample(mom[j].x, mom[j].y, ptn::luminance(v[j].x, v[j].y, v[j].z));
+        }
     }
 #pragma unroll
     for (int j = 0; j < kAccumPix; j++)
-        if (on[j]) p.accum[idx[j]] = acc[j];
+        if (on[j]) {
+            p.accum[idx[j]] = acc[j];
+            if constexpr (MOMENTS) p.moments[idx[j]] = mom[j];
+        }
     // the ACES view of the new image for pt_present_begin (pixels outside the dispatch
     // footprint keep their old value): the same aces_px of the same values as k_aces
     if (p.aces_out) {
@@ -1432,6 +1447,68 @@ __global__ __launch_bounds__(256) void k_aces(const float4* __restrict__ src, uc
     for (int j = 0; j < kAcesPix; j++) {
         const long long i = base + (long long)j * blockDim.x;
         if (i < n) dst[i] = aces_px(v[j]);
+    }
+}
+
+// The noise summary of the local rows (pt_noise): every footprint pixel's moments through
+// ptn::quantise, summed as integers -- exact in any order, so neither the grid nor the arrival
+// order of the atomics can change a field.  A grid-stride loop with the footprint predicate of
+// k_accum_frames, per-thread partials, one 64-lane shuffle reduction per wave (every lane of
+// the block's four full waves takes part: no lane leaves early), the four waves' results added
+// through LDS, and then one set of four device-scope integer atomics per block into the stats
+// block the stream zeroed before.  The atomics all land on one 32-byte block and are the
+// kernel's cost, about 12 ns each: with one set per wave a 1080p summary took 104 us at 2 blocks
+// per CU and 407 us (host round trip) at 8, the time following the number of waves.
+#ifndef PT_NOISE_BPC
+#define PT_NOISE_BPC 2
+#endif
+constexpr int kNoiseBlocksPerCu = PT_NOISE_BPC;   // pt_noise's grid: at most this many blocks per CU
+__global__ __launch_bounds__(256) void k_noise(KParams p, int frames, unsigned target_q, pt_noise_stats* out) {
+    const unsigned n = (unsigned)p.rows_local * (unsigned)p.W;      // < 2^31 (pt_create)
+    const unsigned stride = gridDim.x * blockDim.x;                 // a few blocks per CU: i + stride < 2^32
+    unsigned long long sum_q = 0;
+    unsigned pixels = 0, above = 0, max_q = 0;
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const int crow = (int)(i / (unsigned)p.W), cx = (int)(i - (unsigned)crow * (unsigned)p.W);
+        if (!(cx < p.x_limit && p.row0 + crow * p.row_stride < p.y_limit)) continue;
+        const float2 m = p.moments[i];
+        const unsigned q = ptn::quantise(m.x, m.y, frames);
+        pixels++;
+        sum_q += q;
+        above += q > target_q;
+        max_q = q > max_q ? q : max_q;
+    }
+    // pixels and above: a wave's counts stay below the image's 2^31 pixels -- 32 bits hold them
+    for (int off = 32; off > 0; off >>= 1) {
+        pixels += __shfl_xor(pixels, off, 64);
+        above += __shfl_xor(above, off, 64);
+        const unsigned o = __shfl_xor(max_q, off, 64);
+        max_q = o > max_q ? o : max_q;
+    }
+    sum_q = wave_sum(sum_q);
+    __shared__ unsigned long long s_sum[4];
+    __shared__ unsigned s_pixels[4], s_above[4], s_max[4];
+    const unsigned wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63u) == 0) {
+        s_sum[wave] = sum_q;
+        s_pixels[wave] = pixels;
+        s_above[wave] = above;
+        s_max[wave] = max_q;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (unsigned w = 1; w < 4; w++) {      // a block's counts stay below 2^31 as well
+            sum_q += s_sum[w];
+            pixels += s_pixels[w];
+            above += s_above[w];
+            max_q = s_max[w] > max_q ? s_max[w] : max_q;
+        }
+        if (pixels) {
+            atomicAdd(&out->pixels, (unsigned long long)pixels);
+            atomicAdd(&out->sum_q, sum_q);
+            atomicAdd(&out->above, (unsigned long long)above);
+            atomicMax(&out->max_q, max_q);
+        }
     }
 }
 
@@ -1580,6 +1657,13 @@ struct pt_ctx {
     // holds the view of the current image (set by such a pass, cleared by anything that may
     // change the image or rgba8 afterwards).
     bool presented = false, aces_fuse = false, stage_ok = false;
+    // noise estimate (pt_set_moments): the luminance moments beside accum, the frames folded
+    // into them since the image last restarted (host count), and the summary's device block
+    // and pinned host copy (k_noise)
+    float2* moments = nullptr;
+    int mom_frames = 0;
+    pt_noise_stats* d_noise = nullptr;
+    pt_noise_stats* h_noise = nullptr;
     std::string err;
 };
 
@@ -1702,6 +1786,9 @@ void pt_destroy(pt_ctx* c) {
     free_scene(c);
     (void)hipFree(c->accum); (void)hipFree(c->rgba8); (void)hipFree(c->d_counters); (void)hipFree(c->d_work);
     (void)hipFree(c->d_frame);
+    (void)hipFree(c->moments);
+    (void)hipFree(c->d_noise);
+    if (c->h_noise) (void)hipHostFree(c->h_noise);
     (void)hipFree(c->d_tile_perm);
     (void)hipFree(c->d_tile_cost);
     (void)hipFree(c->d_rgb);
@@ -2286,6 +2373,9 @@ constexpr int kOrderEvery = PT_ORDER_EVERY;   // short launches per tile-order s
 constexpr int kOrderFirst = 8;                // ... and before the first sort after an upload
 constexpr int kProbeFrames = 2, kProbeMin = 64;  // cold long renders: a sorted order after 2 frames
 static bool split_mode(const pt_ctx* c, int n_frames, int group) {
+    // the moments of the noise estimate are kept by the accumulate pass: with them on every
+    // launch is split, also whole-pixel items (tuning key 5 >= n_frames)
+    if (c->moments) return true;
     if (group < n_frames) return true;
     return c->group_force == 0 && n_frames <= kShortLaunch;
 }
@@ -2660,14 +2750,19 @@ static int enqueue_render(pt_ctx* c, int frame_first, int n_frames, int acc_firs
             // a captured graph: its replays are not followed by pt_present_begin's check)
             p.aces_out = (c->aces_fuse && !frame_dev) ? c->rgba8 : nullptr;
             c->stage_ok = p.aces_out != nullptr;
-            if (n_frames > kShortLaunch)
-                hipLaunchKernelGGL((k_accum_frames<kAccumPixLong, kAccumFramesLong>),
-                                   dim3((unsigned)((px + 256 * kAccumPixLong - 1) / (256 * kAccumPixLong))), dim3(256), 0,
+            p.moments = c->moments;
+            const dim3 grid_long((unsigned)((px + 256 * kAccumPixLong - 1) / (256 * kAccumPixLong)));
+            const dim3 grid_short((unsigned)((px + 256 * kAccumPix - 1) / (256 * kAccumPix)));
+            if (n_frames > kShortLaunch && p.moments)
+                hipLaunchKernelGGL((k_accum_frames<kAccumPixLong, kAccumFramesLong, true>), grid_long, dim3(256), 0,
                                    c->stream, p);
+            else if (n_frames > kShortLaunch)
+                hipLaunchKernelGGL((k_accum_frames<kAccumPixLong, kAccumFramesLong>), grid_long, dim3(256), 0,
+                                   c->stream, p);
+            else if (p.moments)
+                hipLaunchKernelGGL((k_accum_frames<kAccumPix, 1, true>), grid_short, dim3(256), 0, c->stream, p);
             else
-                hipLaunchKernelGGL((k_accum_frames<kAccumPix, 1>),
-                                   dim3((unsigned)((px + 256 * kAccumPix - 1) / (256 * kAccumPix))), dim3(256), 0,
-                                   c->stream, p);
+                hipLaunchKernelGGL((k_accum_frames<kAccumPix, 1>), grid_short, dim3(256), 0, c->stream, p);
             if (overlap) {
                 HIPCHK(c, hipEventRecord(c->ev_adone[re], c->stream));
                 c->adone_rec[re] = true;
@@ -2763,6 +2858,10 @@ int pt_render_async(pt_ctx* c, int frame_first, int n_frames, int acc_first) {
     c->presented = false;
     rc = enqueue_frames(c, frame_first, n_frames, acc_first, nullptr, 0);
     if (rc) return rc;
+    if (c->moments) {   // the frames in the moments: they restart where the image does
+        if (!acc_first) c->mom_frames = 0;
+        c->mom_frames += n_frames;
+    }
     HIPCHK(c, hipEventRecord(ev[1], c->stream));
     c->count_pending = c->counting;
     return PT_OK;
@@ -2829,6 +2928,9 @@ int pt_progressive_reset(pt_ctx* c, int next_frame) {
     HIPCHK(c, hipSetDevice(c->cfg.device));
     HIPCHK(c, hipMemcpyAsync(c->d_frame, &next_frame, sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    // frame 1 restarts the image and the moments on the device (resolve_frames); any other
+    // frame continues both
+    if (next_frame == 1) c->mom_frames = 0;
     return PT_OK;
 }
 
@@ -2850,6 +2952,7 @@ int pt_progressive_run(pt_ctx* c, int replays) {
     c->ev_pending.emplace_back(ev[0], ev[1]);
     HIPCHK(c, hipEventRecord(ev[0], c->stream));
     for (int r = 0; r < replays; r++) HIPCHK(c, hipGraphLaunch(c->graph_exec, c->stream));
+    if (c->moments) c->mom_frames += replays * c->graph_frames;
     HIPCHK(c, hipEventRecord(c->ev_fence, c->stream));   // the replays sort the tile order
     c->fence_rec = true;
     HIPCHK(c, hipEventRecord(ev[1], c->stream));
@@ -2984,6 +3087,113 @@ int pt_write_rgba32f(pt_ctx* c, const float* src, size_t bytes) {
     HIPCHK(c, hipSetDevice(c->cfg.device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(c->accum, src, need, hipMemcpyHostToDevice));
+    return PT_OK;
+}
+
+// The noise estimate.  Turning the moments on or off changes which accumulate
+// kernel every later launch runs and whether register-mode launches exist (split_mode), so
+// the context's streams are drained and a captured graph, which bakes the pointer in, is dropped.
+int pt_set_moments(pt_ctx* c, int enable) {
+    if (!c) return PT_E_ARG;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    const size_t px = std::max<size_t>((size_t)c->rows_local * c->cfg.width, 1);
+    c->mom_frames = 0;
+    if ((enable != 0) == (c->moments != nullptr)) {
+        // already so; on again: zeroed behind the passes that may still write them
+        if (c->moments) HIPCHK(c, hipMemsetAsync(c->moments, 0, px * sizeof(float2), c->stream));
+        return PT_OK;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < kMaxSlots; i++)
+        if (c->rstream[i]) HIPCHK(c, hipStreamSynchronize(c->rstream[i]));
+    drop_graph(c);
+    if (!enable) {
+        (void)hipFree(c->moments);
+        c->moments = nullptr;
+        return PT_OK;
+    }
+    if (!c->d_noise) HIPCHK(c, hipMalloc(&c->d_noise, sizeof(pt_noise_stats)));
+    if (!c->h_noise) HIPCHK(c, hipHostMalloc((void**)&c->h_noise, sizeof(pt_noise_stats), hipHostMallocDefault));
+    float2* m = nullptr;
+    HIPCHK(c, hipMalloc(&m, px * sizeof(float2)));
+    hipError_t e = hipMemset(m, 0, px * sizeof(float2));
+    if (e != hipSuccess) {
+        (void)hipFree(m);
+        return fail(c, PT_E_HIP, std::string("hipMemset(moments): ") + hipGetErrorString(e));
+    }
+    c->moments = m;
+    return PT_OK;
+}
+
+int pt_read_moments(pt_ctx* c, float* dst, size_t bytes, int* frames) {
+    if (!c || !dst) return PT_E_ARG;
+    if (!c->moments) return fail(c, PT_E_STATE, "moments are off (pt_set_moments)");
+    const size_t need = (size_t)c->rows_local * c->cfg.width * sizeof(float2);
+    if (bytes < need) return fail(c, PT_E_ARG, "destination too small");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(dst, c->moments, need, hipMemcpyDeviceToHost));
+    if (frames) *frames = c->mom_frames;
+    return PT_OK;
+}
+
+// The summary on the context stream, behind the accumulate passes it depends on: the 32-byte
+// block zeroed, k_noise, the block copied to pinned host memory; then one wait.
+int pt_noise(pt_ctx* c, float target, pt_noise_stats* out) {
+    if (!c || !out) return PT_E_ARG;
+    if (!c->moments) return fail(c, PT_E_STATE, "moments are off (pt_set_moments)");
+    if (c->mom_frames < 2) return fail(c, PT_E_STATE, "the noise estimate needs at least 2 frames");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    HIPCHK(c, hipMemsetAsync(c->d_noise, 0, sizeof(pt_noise_stats), c->stream));
+    const long long px = (long long)c->rows_local * c->cfg.width;
+    if (px > 0) {
+        KParams p;
+        std::memset(&p, 0, sizeof(p));
+        p.W = c->cfg.width;
+        p.H = c->cfg.height;
+        p.row0 = c->cfg.rank;
+        p.row_stride = c->cfg.world;
+        p.rows_local = c->rows_local;
+        p.x_limit = (c->cfg.flags & PT_FLAG_REF_DISPATCH) ? (p.W / 10) * 10 : p.W;
+        p.y_limit = (c->cfg.flags & PT_FLAG_REF_DISPATCH) ? (p.H / 10) * 10 : p.H;
+        p.moments = c->moments;
+        const unsigned blocks = (unsigned)std::min<long long>((px + 255) / 256, (long long)kNoiseBlocksPerCu * c->n_cu);
+        hipLaunchKernelGGL(k_noise, dim3(blocks), dim3(256), 0, c->stream, p, c->mom_frames, ptn::target_q(target),
+                           c->d_noise);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipMemcpyAsync(c->h_noise, c->d_noise, sizeof(pt_noise_stats), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *out = *c->h_noise;
+    out->frames = c->mom_frames;
+    return PT_OK;
+}
+
+int pt_render_until(pt_ctx* c, int frame_first, int acc_first, int batch, int max_frames, float target,
+                    int* frames_done, pt_noise_stats* last) {
+    if (!c || !frames_done) return PT_E_ARG;
+    *frames_done = 0;
+    if (batch < 2 || max_frames < batch || !(target > 0.0f))
+        return fail(c, PT_E_ARG, "pt_render_until: batch >= 2, max_frames >= batch, target > 0");
+    if (!c->scene_ok) return fail(c, PT_E_STATE, "pt_render_until before pt_upload_scene");
+    if (!c->moments) {
+        int rc = pt_set_moments(c, 1);
+        if (rc) return rc;
+    }
+    const unsigned long long tq = ptn::target_q(target);
+    pt_noise_stats s = {0, 0, 0, 0, 0};
+    int done = 0;
+    while (done < max_frames) {
+        const int n = std::min(batch, max_frames - done);
+        int rc = pt_render(c, frame_first + done, n, done ? 1 : acc_first);
+        if (rc) return rc;
+        done += n;
+        *frames_done = done;
+        rc = pt_noise(c, target, &s);
+        if (rc) return rc;
+        if (s.sum_q <= tq * s.pixels) break;      // mean relative error at or below the target
+    }
+    if (last) *last = s;
     return PT_OK;
 }
 

@@ -53,6 +53,19 @@ class ViewerFrame(C.Structure):
                 ("display_mode", C.c_int), ("should_close", C.c_int)]
 
 
+class NoiseStats(C.Structure):
+    """pt_noise_stats (include/pt_api.h): the integer noise summary of a context's pixels."""
+    _fields_ = [("pixels", C.c_ulonglong), ("sum_q", C.c_ulonglong), ("above", C.c_ulonglong),
+                ("max_q", C.c_uint), ("frames", C.c_int)]
+
+    def as_dict(self):
+        """The fields, plus the mean / largest relative error and the fraction above the target."""
+        n = max(int(self.pixels), 1)
+        return dict(pixels=int(self.pixels), sum_q=int(self.sum_q), above=int(self.above), max_q=int(self.max_q),
+                    frames=int(self.frames), mean=int(self.sum_q) / n / 65536.0, max=int(self.max_q) / 65536.0,
+                    above_frac=int(self.above) / n)
+
+
 _lib = None
 _F = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 _I = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
@@ -118,6 +131,12 @@ def lib():
             "pt_progressive_run": (ip, [vp, ip]),
             "pt_set_display_mode": (ip, [vp, ip]),
             "pt_get_config": (ip, [vp, C.POINTER(_Config)]),
+            "pt_set_moments": (ip, [vp, ip]),
+            "pt_read_moments": (ip, [vp, vp, C.c_size_t, C.POINTER(ip)]),
+            "pt_noise": (ip, [vp, fp, C.POINTER(NoiseStats)]),
+            "pt_noise_host": (ip, [_F, vp, C.c_size_t, ip, fp, C.POINTER(NoiseStats)]),
+            "pt_render_until": (ip, [vp, ip, ip, ip, ip, fp, C.POINTER(ip), C.POINTER(NoiseStats)]),
+            "pt_group_noise": (ip, [vp, fp, C.POINTER(NoiseStats)]),
             "pt_group_create": (ip, [C.POINTER(vp), ip, C.POINTER(vp)]),
             "pt_group_destroy": (None, [vp]),
             "pt_group_last_error": (C.c_char_p, [vp]),
@@ -420,6 +439,32 @@ class PathTracer:
         if sync:
             self.sync()
 
+    def set_moments(self, enable=True):
+        """Keep per-pixel luminance moments beside the image (pt_set_moments): the noise estimate
+        of noise() / render_until().  Never changes the image."""
+        self._check(lib().pt_set_moments(self.h, int(bool(enable))))
+
+    def read_moments(self):
+        """-> ((rows_local, W, 2) float32 of (S1, S2), frames folded in)."""
+        out = np.zeros((self.rows_local, self.width, 2), np.float32)
+        n = C.c_int()
+        self._check(lib().pt_read_moments(self.h, out.ctypes.data, out.nbytes, C.byref(n)))
+        return out, n.value
+
+    def noise(self, target):
+        """pt_noise: the integer noise summary of the local rows as a dict (NoiseStats.as_dict)."""
+        s = NoiseStats()
+        self._check(lib().pt_noise(self.h, float(target), C.byref(s)))
+        return s.as_dict()
+
+    def render_until(self, target, batch=16, max_frames=1024, frame_first=1, accumulate_first=0):
+        """pt_render_until: frames in batches until the mean relative error is at most `target`
+        (or max_frames) -> (frames_done, summary dict)."""
+        done, s = C.c_int(), NoiseStats()
+        self._check(lib().pt_render_until(self.h, int(frame_first), int(accumulate_first), int(batch), int(max_frames),
+                                          float(target), C.byref(done), C.byref(s)))
+        return done.value, s.as_dict()
+
     def diag(self):
         """Lane utilisation per kernel phase from the last counting render."""
         v = np.zeros(16, np.uint64)
@@ -574,6 +619,12 @@ class Group:
         arr = np.ctypeslib.as_array(p, shape=(self.H, self.W, 4))
         return arr.copy() if copy else arr
 
+    def noise(self, target):
+        """pt_group_noise: the contexts' noise summaries added (PathTracer.noise's dict)."""
+        s = NoiseStats()
+        self._check(lib().pt_group_noise(self.h, float(target), C.byref(s)))
+        return s.as_dict()
+
     def stats(self):
         ms, b = C.c_double(), C.c_size_t()
         self._check(lib().pt_group_stats(self.h, C.byref(ms), C.byref(b)))
@@ -583,6 +634,24 @@ class Group:
         if getattr(self, "h", None) is not None and self.h.value:
             lib().pt_group_destroy(self.h)
         self.h = C.c_void_p()
+
+
+def noise_host(moments, frames, target, in_footprint=None):
+    """pt_noise_host: the noise summary of (..., 2) float32 moments on the host (no device) -- the
+    per-pixel function is the device kernel's own code.  in_footprint: one flag per pixel."""
+    m = np.ascontiguousarray(moments, np.float32).reshape(-1)
+    n = m.size // 2
+    fp = None
+    if in_footprint is not None:
+        fp = np.ascontiguousarray(np.asarray(in_footprint).reshape(-1) != 0, np.uint8)
+        if fp.size != n:
+            raise ValueError("in_footprint must hold one flag per pixel")
+    s = NoiseStats()
+    rc = lib().pt_noise_host(m if n else np.zeros(2, np.float32), None if fp is None else fp.ctypes.data, n,
+                             int(frames), float(target), C.byref(s))
+    if rc:
+        raise PTError(rc, "pt_noise_host: frames must be >= 2")
+    return s.as_dict()
 
 
 def group_plan(devices, ranks):
