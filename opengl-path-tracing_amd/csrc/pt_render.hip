@@ -20,8 +20,10 @@
 //   leaf code  : k << 2 | coplanar << 1 | single (k = leaf pair index, slots 2k and 2k+1)
 //   mat   48 B : {color.rgb, smoothness}, {emission*strength, specProb}, {specular.rgb, 0}
 //   sphere 32 B: {c.xyz, r*r}, {matIdx, 0, 0, 0}
+#include "pt_launch_plan.h"
 #include "pt_math.h"
 #include "pt_noise.h"
+#include "pt_render_kernels.h"
 #include "pt_wide.h"
 #include "../../include/pt_api.h"
 #include "../../include/pt_scene.h"
@@ -35,6 +37,10 @@
 
 using pt::f3;
 using pt::mk;
+using ptl::kAccumPix;
+using ptl::kAccumPixLong;
+using ptl::kPadNodes;
+using ptl::kPullBatch;
 
 namespace {
 
@@ -276,14 +282,7 @@ struct SceneView {
 // The global-memory walk keeps the reference links (node indices, a = ~code at a leaf):
 // there the loads, not the selects, set the pace, and the reference form measured faster.
 extern __shared__ float4 g_lds[];   // the state-machine kernel's scene copy (nodes first)
-// Scenes of at most kPadNodes nodes get walk images padded to kPadNodes nodes per plane, so
-// the hi half of a node sits at the compile-time offset 16 * kPadNodes from its lo half (an
-// immediate ds_read_b128 offset instead of an address add per walk step).  67: consecutive
-// images start 134 16-B granules apart, 6 mod 16, spreading them over the LDS bank groups.
-#ifndef PT_PAD_NODES
-#define PT_PAD_NODES 67
-#endif
-constexpr int kPadNodes = PT_PAD_NODES;
+// (scenes of at most kPadNodes nodes: images padded to that count, pt_launch_plan.h)
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) const v4f lds_v4f;
 template <bool LDS, bool PADN = false>
@@ -537,7 +536,6 @@ __device__ __forceinline__ void leaf_pair_tests(const SceneView& S, bool at, int
 // next node, same t), so results are bit-identical; only lane interleaving changes.
 // =====================================================================================
 enum : int { ST_DONE = 0, ST_TRAV = 1, ST_LEAF = 2, ST_SHADE = 3 };
-constexpr unsigned kPullBatch = 32;
 // work-queue head stride (unsigned): each context stream / overlap slot has its own head on
 // its own 128-B line
 constexpr int kQueueStride = 32;
@@ -1344,15 +1342,11 @@ __device__ __forceinline__ uchar4 aces_px(float4 v) {
 // Each thread takes kAccumPix pixels a block-width apart (coalesced), their loads issued
 // together: beside a running render this pass gets a few block slots per CU, and with one
 // pixel per thread it was latency-bound (about 100 us for a 1080p frame against 15 us alone).
-#ifndef PT_ACCUM_PIX
-#define PT_ACCUM_PIX 4
-#endif
-constexpr int kAccumPix = PT_ACCUM_PIX;
 // Long launches (more than kShortLaunch frames): 2 pixels per thread and 8 frames per load
 // group (same-process A/B, a 1080p/8 share's 1024-frame launch: +1.6% for the whole render
 // against one frame per group, +1.1% with 4 x 4; the full 1080p image unchanged).  Short
 // launches keep 4 pixels and one frame per group (the pass beside the next one-frame render).
-constexpr int kAccumPixLong = 2, kAccumFramesLong = 8;
+constexpr int kAccumFramesLong = 8;   // (pixels per thread: ptl::kAccumPix, kAccumPixLong)
 // MOMENTS: the per-frame luminance moments of the noise estimate (pt_noise.h) are kept beside
 // the image -- loaded with it (or zero where it restarts), updated after each frame's
 // accumulate() in the same frame order, stored with it.  The colours are already in registers
@@ -1515,41 +1509,19 @@ __global__ __launch_bounds__(256) void k_noise(KParams p, int frames, unsigned t
 }  // namespace
 
 // ===================================================================== host side
-// Stage the scene in LDS up to this size.  One workgroup may hold all 160 KiB of a CU's LDS
-// on gfx950; a copy too large for the resident waves' worth of 256-thread workgroups is
-// shared by wider ones (lds_threads), so mid-size scenes keep the LDS walk at 4+ waves per
-// SIMD instead of the global-memory walk.
-#ifndef PT_TILE_AUTO
-#define PT_TILE_AUTO 0      // 1: 16 x 4 tiles for LDS scenes (measured equal to 8 x 8, ensure_tiles)
-#endif
-#ifndef PT_LDS_SCENE_MAX_KIB
-#define PT_LDS_SCENE_MAX_KIB 152
-#endif
-#ifndef PT_LDS_WIDE
-#define PT_LDS_WIDE 1
-#endif
-constexpr size_t kLdsSceneMax = (size_t)PT_LDS_SCENE_MAX_KIB * 1024;
-constexpr size_t kLdsSceneSmall = 48 * 1024;  // staged by 256-thread workgroups in every configuration
+// Launch policy (LDS staging, workgroup, group, queue batch, the kernel key) lives in
+// pt_launch_plan.{h,cpp}; this file fills KParams from its plan and does the stateful work.
+using ptl::kAutoSlots;
+using ptl::kMaxSlots;
+using ptl::kShortLaunch;
 // global-memory scenes: the first kTopNodes device nodes (breadth-first from the root) are
 // staged in LDS, 24 KiB per workgroup (6 workgroups per CU stay resident)
 constexpr int kTopNodes = 768;
-// overlapped short launches: render slots (tuning key 9).  A slot's scratch is reused only
-// after the accumulate pass that read it.  Measured on 1080p Cornell one-frame launches (ms per
-// frame, round 3): 1 slot (no overlap) 0.80, 2 slots 0.60, 3 slots 0.62, 4 slots 0.66 -- more
-// slots put more renders in flight, whose blocks then held the CUs before the accumulate passes
-// (and with them the slots) came free.  With the blocks-per-CU cap (key 18) and presentation
-// on the context stream (round 4; render only / every frame shown at lag 2): 2 slots at 6
-// blocks per CU 0.516 / 0.522-0.547, 3 slots at 6 0.509 / 0.525, 3 at 5 0.505 / 0.527, 3 at 4
-// 0.503 / 0.532, 4 at 4-5 0.615 / 0.59.
-constexpr int kMaxSlots = 4, kAutoSlots = 3;
 // Scratch ring of overlapped launches: each launch takes the next entry (colour scratch, queue
 // head, render / accumulate events) of a ring kRingMult times as long as the render streams, so
 // a render waits for the accumulate pass of the launch kRingMult * slots back, not of the one
 // that last used its stream (which the stream order already puts before it).
-#ifndef PT_RING_MULT
-#define PT_RING_MULT 2
-#endif
-constexpr int kRingMult = PT_RING_MULT, kRingMax = kRingMult * kMaxSlots;
+constexpr int kRingMult = 2, kRingMax = kRingMult * kMaxSlots;
 constexpr size_t kQueueSet = kQueueStride;   // unsigned per queue head
 
 constexpr int kPresentBufs = 4;   // pt_present_begin buffers
@@ -1567,19 +1539,12 @@ struct pt_ctx {
     float4 *d_nodes = nullptr, *d_tris = nullptr, *d_mats = nullptr, *d_spheres = nullptr;
     float4* d_walk_lds = nullptr;   // LDS walk image (DevScene)
     float4* d_walk_sk = nullptr;    // ... the culling walk's copy with its sink image
-    size_t lds_bytes_sk = 0;
+    ptl::SceneFacts sf;             // what pt_upload_scene learned (the launch planner's input)
+    ptl::Tuning tun;                // pt_set_tuning values and the kernel variant
     // the wide walk of global-memory scenes (pt_wide.h; nested trees inside the scene guard):
     // records, exact leaf boxes, and the node / triangle arrays with leaf slots numbered by the
     // wide tree's index (the binary walk of the lanes outside the guard shares them)
     float4 *d_wrec = nullptr, *d_wlbox = nullptr, *d_nodesw = nullptr, *d_trisw = nullptr;
-    bool wide_ok = false;
-    int n_wide = 0;                 // wide index space (records + leaves)
-    float wide_cw[3] = {0, 0, 0};
-    int wide_off = 0;               // tuning key 16: 1 = the binary global walk
-    int cert_off = 0;               // tuning key 19: 1 = always run the exact leaf re-test
-    bool leaf_cert_ok = false;      // every leaf box contains its triangles' vertices (pt_wide.h certificate)
-    int wide_threads = 0;           // tuning key 17: threads per block of the wide walk (0 = automatic)
-    int overlap_bpc = 0;            // tuning key 18: render blocks per CU of overlapped short launches (0 = automatic)
     unsigned long long* d_counters = nullptr;
     unsigned int* d_work = nullptr;
     int* d_frame = nullptr;                      // progressive graph frame counter
@@ -1589,36 +1554,17 @@ struct pt_ctx {
     unsigned* d_tile_perm = nullptr;
     int n_tiles = 0, tiles_x = 1;
     int tile_shift = 0, tile_key = 0;   // tile shape (KParams::tile_shift) and tuning key 20 (0 = automatic)
-    bool adaptive = true;
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
     int graph_frames = 0;
-    int n_nodes = 0, n_spheres = 0, n_mats = 0, n_slots = 0, scene_fast = 0, n_top = 0, walk_np = 1;
-    float root_box[6] = {0, 0, 0, 0, 0, 0};
-    int root_child = -1;
-    // the tree is a full binary tree threaded in preorder whose internal boxes contain their
-    // children's (pt_bvh_culling_ok): the LDS walk may cull with slab_oct_cons (tuning key 15 = 1: off)
-    bool walk_nested = false;
-    int cons_off = 0;
-    float cons_m[3] = {0, 0, 0};   // KParams::cons_m
-    size_t lds_bytes = 0;
     unsigned persist_blocks = 2048;
     int order_skip = 0;             // short launches since the last tile-order sort
     bool order_sorted = false;      // a sort ran since the scene upload
-    // 0 = automatic: 52/44 when the scene is staged in LDS (best on C2 since the octant walk),
-    // 20/24 when the walk reads global memory (re-swept after the leaf compaction: +2% on
-    // the C3 stand-in, +3% on C4 over 16/32; leaf 20 re-swept in round 2: C3 +1.3%, C4 +0.6%
-    // over 16); walk floor 5 / 6 (LDS: 8 until the culling walk
-    // made a walk step cheaper; re-swept with the sink walk: 5 +0.9% over 3, 2-8 within 1%)
-    // (+0.8% on C2, +0.5% on C3 over no floor) -- tools/probe.py sweeps
-    int leaf_thresh = 0, shade_thresh = 0, minw = 0, trav_floor = 0, compact_max = 63, pull_batch = 0;
-    // frame-split work items (KParams::group): 0 = automatic, n = frames per item
-    int group_force = 0;
     int n_cu = 0;
     float* d_rgb = nullptr;        // per-(frame, pixel) colours of the frame-split mode
     size_t rgb_bytes = 0;
     // overlapped short launches (enqueue_render): the render kernels of consecutive short
-    // renders rotate over `n_slots` streams with their own colour scratch and queue counter,
+    // renders rotate over `tun.overlap_slots` streams with their own colour scratch and queue counter,
     // so frame f+1 renders while frame f's launch drains; k_accum_frames stays on `stream`
     // (created with the highest priority, so its small grid is dispatched as soon as render
     // blocks retire) in frame order
@@ -1632,17 +1578,12 @@ struct pt_ctx {
     bool adone_rec[kRingMax] = {}, fence_rec = false;
     int slot = 0;
     int ring = 0;                   // next scratch-ring entry of an overlapped launch
-    int overlap_slots = kAutoSlots;   // tuning key 9 (1 = one stream, no overlap)
-    // frame-split scratch budget: a render needing more is issued as back-to-back launches
-    // (tuning key 8; default min(32 GiB, a quarter of the device memory))
-    size_t scratch_budget = 0;
     // a captured graph bakes in the scratch pointer it was captured with: that buffer stays
     // alive (owned here once ensure_rgb has moved on to a larger one) until drop_graph
     float* graph_rgb = nullptr;
     std::vector<float*> graph_owned;
     bool scene_ok = false, cam_ok = false, counting = false;
     float cam[12] = {0};
-    int variant = 0;
     float last_ms = 0.0f;
     unsigned long long last_counts[16] = {0};
     bool count_pending = false;
@@ -1717,8 +1658,8 @@ static void free_scene(pt_ctx* c) {
     (void)hipFree(c->d_wrec); (void)hipFree(c->d_wlbox); (void)hipFree(c->d_nodesw); (void)hipFree(c->d_trisw);
     c->d_nodes = c->d_tris = c->d_mats = c->d_spheres = c->d_walk_lds = c->d_walk_sk = nullptr;
     c->d_wrec = c->d_wlbox = c->d_nodesw = c->d_trisw = nullptr;
-    c->wide_ok = false;
-    c->n_wide = 0;
+    c->sf.wide_ok = false;
+    c->sf.n_wide = 0;
     c->scene_ok = false;
 }
 
@@ -1766,7 +1707,7 @@ int pt_create(const pt_config* cfg, pt_ctx** out) {
     {
         size_t total_mem = 0;
         HIPCHK(c, hipDeviceTotalMem(&total_mem, cfg->device));
-        c->scratch_budget = std::min<size_t>(32ull << 30, total_mem / 4);
+        c->tun.scratch_budget = std::min<size_t>(32ull << 30, total_mem / 4);
     }
     {
         int rc = set_tiles(c, 0);   // 8 x 8 until a scene picks the automatic shape (ensure_tiles)
@@ -2080,8 +2021,8 @@ int pt_upload_scene(pt_ctx* c, const float* tris, int n_tris, const float* bvh, 
         HIPCHK(c, hipMemcpy(c->d_wlbox, wt.lbox.data(), nr * 2 * sizeof(float4), hipMemcpyHostToDevice));
         HIPCHK(c, hipMemcpy(c->d_nodesw, dnw.data(), dnw.size() * sizeof(float4), hipMemcpyHostToDevice));
         HIPCHK(c, hipMemcpy(c->d_trisw, dtw.data(), dtw.size() * sizeof(float4), hipMemcpyHostToDevice));
-        c->n_wide = wt.n_index;
-        std::memcpy(c->wide_cw, wt.cw, sizeof(c->wide_cw));
+        c->sf.n_wide = wt.n_index;
+        std::memcpy(c->sf.wide_cw, wt.cw, sizeof(c->sf.wide_cw));
     }
     if (nested) {
         HIPCHK(c, hipMalloc(&c->d_walk_sk, dsk.size() * sizeof(float4)));
@@ -2097,38 +2038,38 @@ int pt_upload_scene(pt_ctx* c, const float* tris, int n_tris, const float* bvh, 
     HIPCHK(c, hipMemcpy(c->d_tris, dt.data(), dt.size() * sizeof(float4), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->d_mats, dm.data(), dm.size() * sizeof(float4), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->d_spheres, ds.data(), ds.size() * sizeof(float4), hipMemcpyHostToDevice));
-    c->n_nodes = n_nodes;
-    c->n_spheres = n_spheres;
-    c->n_mats = n_mats;
-    c->n_slots = 2 * n_leaves;
-    c->n_top = std::min(n_nodes, kTopNodes);
+    c->sf.n_nodes = n_nodes;
+    c->sf.n_spheres = n_spheres;
+    c->sf.n_mats = n_mats;
+    c->sf.n_slots = 2 * n_leaves;
+    c->sf.n_top = std::min(n_nodes, kTopNodes);
     // exact-reciprocal slab guard, scene half: every box coordinate is 0
     // or has magnitude in [2^-40, 2^60], and min <= max on every axis (the octant images'
     // near-first order, slab_oct)
-    c->scene_fast = 1;
-    for (int i = 0; i < n_nodes && c->scene_fast; i++) {
+    c->sf.scene_fast = 1;
+    for (int i = 0; i < n_nodes && c->sf.scene_fast; i++) {
         const float* nd = bvh + 12 * (size_t)i;
         for (int q = 0; q < 7; q++) {
             if (q == 3) continue;
             float a = std::fabs(nd[q]);
-            if (!(nd[q] == 0.0f || (a >= 0x1p-40f && a <= 0x1p60f))) { c->scene_fast = 0; break; }
+            if (!(nd[q] == 0.0f || (a >= 0x1p-40f && a <= 0x1p60f))) { c->sf.scene_fast = 0; break; }
         }
-        if (!(nd[0] <= nd[4] && nd[1] <= nd[5] && nd[2] <= nd[6])) c->scene_fast = 0;
+        if (!(nd[0] <= nd[4] && nd[1] <= nd[5] && nd[2] <= nd[6])) c->sf.scene_fast = 0;
     }
-    c->walk_nested = nested;
-    c->wide_ok = wide;
+    c->sf.walk_nested = nested;
+    c->sf.wide_ok = wide;
     // the leaf re-test certificate (ptw::leaf_certificate) needs each leaf box to contain its
     // triangles' vertices -- the reference builder expands leaf boxes over them (bvh.h:29-52);
     // an uploaded tree is checked, not assumed
-    c->leaf_cert_ok = true;
-    for (int i = 0; i < n_nodes && c->leaf_cert_ok; i++) {
+    c->sf.leaf_cert_ok = true;
+    for (int i = 0; i < n_nodes && c->sf.leaf_cert_ok; i++) {
         const float* nd = bvh + 12 * (size_t)i;
         if (!(nd[8] > -1.0f)) continue;
-        for (int k = 0; k < 2 && c->leaf_cert_ok; k++) {
+        for (int k = 0; k < 2 && c->sf.leaf_cert_ok; k++) {
             const float* t = tris + 16 * (size_t)(int)nd[8 + k];
             for (int v = 0; v < 3; v++)
                 for (int q = 0; q < 3; q++)
-                    if (!(nd[q] <= t[4 * v + q] && t[4 * v + q] <= nd[4 + q])) c->leaf_cert_ok = false;
+                    if (!(nd[q] <= t[4 * v + q] && t[4 * v + q] <= nd[4 + q])) c->sf.leaf_cert_ok = false;
         }
     }
     c->order_sorted = false;      // the next sort pools the new scene's first short launches
@@ -2136,20 +2077,20 @@ int pt_upload_scene(pt_ctx* c, const float* tris, int n_tris, const float* bvh, 
     if (n_nodes > 0) {   // every box lies in the root box (nested): M_i bounds each |coordinate|
         for (int q = 0; q < 3; q++) {
             const double m = std::max(std::fabs((double)bvh[q]), std::fabs((double)bvh[4 + q]));
-            c->cons_m[q] = (float)std::ldexp(m * (1.0 + 0x1p-20), -19);   // rounded: within 2^-24 relative
+            c->sf.cons_m[q] = (float)std::ldexp(m * (1.0 + 0x1p-20), -19);   // rounded: within 2^-24 relative
         }
     }
-    c->walk_np = (int)N;
-    c->lds_bytes = (size_t)(16 * N + 4 * c->n_slots + 3 * n_mats + 2 * n_spheres) * sizeof(float4);
-    c->lds_bytes_sk = c->lds_bytes + 2 * N * sizeof(float4);
-    c->root_child = -1;
+    c->sf.walk_np = (int)N;
+    c->sf.lds_bytes = (size_t)(16 * N + 4 * c->sf.n_slots + 3 * n_mats + 2 * n_spheres) * sizeof(float4);
+    c->sf.lds_bytes_sk = c->sf.lds_bytes + 2 * N * sizeof(float4);
+    c->sf.root_child = -1;
     if (n_nodes > 0) {
         const float4 r0 = dn[0], r1 = dn[1];
         const float box[6] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y};
-        std::memcpy(c->root_box, box, sizeof(box));
+        std::memcpy(c->sf.root_box, box, sizeof(box));
         int a;
         std::memcpy(&a, &r1.z, 4);
-        c->root_child = a >= 0 ? a : -1;
+        c->sf.root_child = a >= 0 ? a : -1;
     }
     c->scene_ok = true;
     return PT_OK;
@@ -2192,21 +2133,62 @@ int pt_set_kernel(pt_ctx* c, int variant) {
     if (variant != 0 && variant != 3)
         return fail(c, PT_E_ARG, "unknown kernel variant (0 state machine, 3 state machine with the scene kept in "
                                  "global memory)");
-    c->variant = variant;
+    c->tun.variant = variant;
     drop_graph(c);
     return PT_OK;
 }
 
+// The plain integer keys of pt_set_tuning: a value `ok` accepts goes to its Tuning member,
+// any other fails with `msg`.  A key may have several rows, checked in order.
+struct TuningKey {
+    int key;
+    int ptl::Tuning::*member;       // null: a check only
+    bool (*ok)(int);
+    const char* msg;
+    bool drops_graph;               // a captured graph bakes the value in
+};
+static bool in_0_1(int v) { return v == 0 || v == 1; }
+static bool in_0_64(int v) { return v >= 0 && v <= 64; }
+static const char kThresholdMsg[] = "threshold must be in 1..64 (0 = automatic)";
+static const TuningKey kTuningKeys[] = {
+    {0, &ptl::Tuning::leaf_thresh, in_0_64, kThresholdMsg, true},
+    {1, &ptl::Tuning::shade_thresh, in_0_64, kThresholdMsg, true},
+    {3, nullptr, in_0_64, kThresholdMsg, true},
+    {3, &ptl::Tuning::minw, [](int v) { return v == 0 || (v >= 5 && v <= 8); }, "waves per SIMD must be 5..8 (0 = auto)", true},
+    {4, &ptl::Tuning::pull_batch, [](int v) { return v >= 0 && v <= 1024; }, "pull batch must be 1..1024 (0 = auto)", true},
+    {5, &ptl::Tuning::group_force, [](int v) { return v >= 0; }, "frames per work item must be >= 1 (0 = automatic)", true},
+    {6, &ptl::Tuning::trav_floor, in_0_64, kThresholdMsg, true},
+    {7, &ptl::Tuning::compact_max, [](int v) { return v >= 0 && v <= 63; }, "compaction limit must be in 0..63", true},
+    {15, &ptl::Tuning::cons_off, in_0_1, "culling walk: 0 = automatic, 1 = off", true},
+    {16, &ptl::Tuning::wide_off, in_0_1, "wide global walk: 0 = automatic, 1 = off", true},
+    {17, &ptl::Tuning::wide_threads, [](int v) { return v == 0 || v == 256 || v == 512 || v == 768 || v == 1024; },
+     "wide walk workgroup: 256, 512, 768 or 1024 threads (0 = automatic)", true},
+    {18, &ptl::Tuning::overlap_bpc, [](int v) { return v >= 0 && v <= 8; },
+     "overlapped render blocks per CU must be 1..8 (0 = automatic)", false},
+    {19, &ptl::Tuning::cert_off, in_0_1, "leaf re-test certificate: 0 = automatic, 1 = off", true},
+};
+
 int pt_set_tuning(pt_ctx* c, int key, int value) {
     if (!c) return PT_E_ARG;
+    const TuningKey* hit = nullptr;
+    for (const TuningKey& k : kTuningKeys) {
+        if (k.key != key) continue;
+        if (!k.ok(value)) return fail(c, PT_E_ARG, k.msg);
+        hit = &k;
+    }
+    if (hit) {
+        c->tun.*hit->member = value;
+        if (hit->drops_graph) drop_graph(c);
+        return PT_OK;
+    }
     if (key == 8) {
         if (value < 0) return fail(c, PT_E_ARG, "scratch budget (MiB) must be >= 0 (0 = automatic)");
         if (value == 0) {
             size_t total_mem = 0;
             HIPCHK(c, hipDeviceTotalMem(&total_mem, c->cfg.device));
-            c->scratch_budget = std::min<size_t>(32ull << 30, total_mem / 4);
+            c->tun.scratch_budget = std::min<size_t>(32ull << 30, total_mem / 4);
         } else {
-            c->scratch_budget = (size_t)value << 20;
+            c->tun.scratch_budget = (size_t)value << 20;
         }
         drop_graph(c);
         return PT_OK;
@@ -2216,27 +2198,9 @@ int pt_set_tuning(pt_ctx* c, int key, int value) {
             return fail(c, PT_E_ARG, "overlap slots must be 1..4 (1 = off, 0 = automatic)");
         HIPCHK(c, hipSetDevice(c->cfg.device));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->overlap_slots = value ? value : kAutoSlots;
+        c->tun.overlap_slots = value ? value : kAutoSlots;
         c->slot = 0;
         c->ring = 0;
-        return PT_OK;
-    }
-    if (key == 15) {
-        if (value != 0 && value != 1) return fail(c, PT_E_ARG, "culling walk: 0 = automatic, 1 = off");
-        c->cons_off = value;
-        drop_graph(c);
-        return PT_OK;
-    }
-    if (key == 18) {
-        if (value < 0 || value > 8) return fail(c, PT_E_ARG, "overlapped render blocks per CU must be 1..8 (0 = automatic)");
-        c->overlap_bpc = value;
-        return PT_OK;
-    }
-    if (key == 17) {
-        if (value != 0 && value != 256 && value != 512 && value != 768 && value != 1024)
-            return fail(c, PT_E_ARG, "wide walk workgroup: 256, 512, 768 or 1024 threads (0 = automatic)");
-        c->wide_threads = value;
-        drop_graph(c);
         return PT_OK;
     }
     if (key == 20) {
@@ -2245,98 +2209,33 @@ int pt_set_tuning(pt_ctx* c, int key, int value) {
         HIPCHK(c, hipSetDevice(c->cfg.device));
         return ensure_tiles(c);
     }
-    if (key == 19) {
-        if (value != 0 && value != 1) return fail(c, PT_E_ARG, "leaf re-test certificate: 0 = automatic, 1 = off");
-        c->cert_off = value;
-        drop_graph(c);
-        return PT_OK;
+    // (as ever, the threshold range is checked before the key)
+    if (!in_0_64(value)) return fail(c, PT_E_ARG, kThresholdMsg);
+    if (key != 2) return fail(c, PT_E_ARG, "unknown tuning key");
+    // a learned order stays when the setting does not change (re-applying the default must
+    // not send the next long render back through the cold probe launch)
+    if ((value != 0) == c->tun.adaptive) return PT_OK;
+    c->tun.adaptive = value != 0;
+    c->order_sorted = false;
+    c->order_skip = 0;
+    if (!c->tun.adaptive && c->n_tiles > 0) {       // back to raster order
+        std::vector<unsigned> ident(c->n_tiles);
+        for (int i = 0; i < c->n_tiles; i++) ident[i] = pack_tile(c, (unsigned)i);
+        HIPCHK(c, hipSetDevice(c->cfg.device));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpy(c->d_tile_perm, ident.data(), ident.size() * sizeof(unsigned), hipMemcpyHostToDevice));
     }
-    if (key == 16) {
-        if (value != 0 && value != 1) return fail(c, PT_E_ARG, "wide global walk: 0 = automatic, 1 = off");
-        c->wide_off = value;
-        drop_graph(c);
-        return PT_OK;
-    }
-    if (key == 5) {
-        if (value < 0) return fail(c, PT_E_ARG, "frames per work item must be >= 1 (0 = automatic)");
-        c->group_force = value;
-        drop_graph(c);
-        return PT_OK;
-    }
-    if (key == 4) {
-        if (value < 0 || value > 1024) return fail(c, PT_E_ARG, "pull batch must be 1..1024 (0 = auto)");
-        c->pull_batch = value;
-        drop_graph(c);
-        return PT_OK;
-    }
-    if (key == 7) {
-        if (value < 0 || value > 63) return fail(c, PT_E_ARG, "compaction limit must be in 0..63");
-        c->compact_max = value;
-        drop_graph(c);
-        return PT_OK;
-    }
-    if (value < 0 || value > 64) return fail(c, PT_E_ARG, "threshold must be in 1..64 (0 = automatic)");
-    if (key == 0) c->leaf_thresh = value;
-    else if (key == 1) c->shade_thresh = value;
-    else if (key == 6) c->trav_floor = value;
-    else if (key == 3) {
-        if (value != 0 && (value < 5 || value > 8)) return fail(c, PT_E_ARG, "waves per SIMD must be 5..8 (0 = auto)");
-        c->minw = value;
-    }
-    else if (key == 2) {
-        // a learned order stays when the setting does not change (re-applying the default must
-        // not send the next long render back through the cold probe launch)
-        if ((value != 0) == c->adaptive) return PT_OK;
-        c->adaptive = value != 0;
-        c->order_sorted = false;
-        c->order_skip = 0;
-        if (!c->adaptive && c->n_tiles > 0) {       // back to raster order
-            std::vector<unsigned> ident(c->n_tiles);
-            for (int i = 0; i < c->n_tiles; i++) ident[i] = pack_tile(c, (unsigned)i);
-            HIPCHK(c, hipSetDevice(c->cfg.device));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            HIPCHK(c, hipMemcpy(c->d_tile_perm, ident.data(), ident.size() * sizeof(unsigned), hipMemcpyHostToDevice));
-        }
-    }
-    else return fail(c, PT_E_ARG, "unknown tuning key");
     drop_graph(c);
     return PT_OK;
 }
 
-// Frames per work item of the state-machine kernel (KParams::group).  Items of a few frames
-// keep every resident lane busy to the end of a launch and let the per-GPU share of a
-// multi-GPU split (fewer pixels than lanes at 1080p/8) use the whole chip; the per-frame
-// colours go to a buffer and k_accum_frames applies the running mean in frame order.
-// Measured (C2 scene, 64-frame launches): 8 frames per item +6% over whole-pixel items on
-// one GPU, 2-4 frames +85% on a 1080p/8 share; so ~16 items per resident lane, capped at
-// 16 frames (4 for global-memory scenes).  group == n_frames is the register mode (a lane owns all frames of a pixel and
-// accumulates in registers).  The counting build follows the same plan: with whole-pixel
-// items a 1080p/8 share of a 1024-frame launch would run each lane through 1024 frames
-// in sequence (minutes).
-// Whether the state-machine kernel stages the scene in LDS:
-// up to kLdsSceneSmall always; up to kLdsSceneMax when wide workgroups share the copy
-// (lds_threads' configuration).  Variant 3 forces the global-memory walk.
-static bool lds_staged(const pt_ctx* c) {
-    if (c->variant == 3) return false;
-    if (c->lds_bytes <= kLdsSceneSmall) return true;
-    return PT_LDS_WIDE && !c->counting && !c->minw && c->cfg.rays_per_pixel == 1 && c->lds_bytes <= kLdsSceneMax;
-}
-
-// Round 6: the frames per item follow the frames each resident lane renders in the launch,
-// F = pixels * frames / resident lanes.  An item costs a fixed pull and set-up o plus g frames
-// of c each, and a launch ends in a tail of about half an item, so the time per lane is about
-// F c + (F / g) o + g c / 2: least at g = sqrt(2 F o / c).  Fitted to same-process A/Bs of C2's
-// 1024-frame launch (profiles/ab/r06f_*): a 1080p/8 share (F = 578) is fastest at 9-12 frames
-// per item (+1.4% over 16), a 1080p/4 share (F = 1157) at 12, the whole image (F = 4628) at
-// 16 or more; global-memory scenes cost about 5x more per frame (c), so about sqrt(5) fewer.
-// The caps: C2 16 +0.5% over 8; C3 stand-in 4 +8% over 8.
-// The work queue's tile shape (set_tiles): tuning key 20, else 8 x 8 (with PT_TILE_AUTO, 16 x 4
-// for scenes staged in LDS).  Measured with the builds in alternating order (ABBA, profiles/ab/
-// r06n_*): 16 x 4 and 8 x 8 equal within 0.1% on C2 and C5; the +0.4..0.6% of the first A/Bs
+// The work queue's tile shape (set_tiles): tuning key 20, else 8 x 8.  16 x 4 tiles for scenes
+// staged in LDS measured equal: with the builds in alternating order (ABBA, profiles/ab/
+// r06n_*) 16 x 4 and 8 x 8 are within 0.1% on C2 and C5; the +0.4..0.6% of the first A/Bs
 // (r06k_*, r06l_*, r06m_*) was tools/ab_inproc.py's first-position bias.  A shape change drains
 // the context's streams and drops a captured graph (which holds the tile arrays).
 static int ensure_tiles(pt_ctx* c) {
-    const int want = c->tile_key ? c->tile_key - 1 : ((PT_TILE_AUTO && c->scene_ok && lds_staged(c)) ? 1 : 0);
+    const int want = c->tile_key ? c->tile_key - 1 : 0;
     if (want == c->tile_shift) return PT_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int i = 0; i < kMaxSlots; i++)
@@ -2345,46 +2244,26 @@ static int ensure_tiles(pt_ctx* c) {
     return set_tiles(c, want);
 }
 
-static int plan_group(const pt_ctx* c, int n_frames) {
-    if (c->group_force > 0) return std::min(c->group_force, n_frames);
-    const int waves = c->minw ? c->minw : (lds_staged(c) ? 7 : 6);
-    const double lanes = (double)c->n_cu * 4.0 * waves * 64.0;
-    const double px = (double)c->rows_local * c->cfg.width;
-    const bool lds_scene = lds_staged(c);
-    const double F = px * n_frames / lanes;
-    int g = (int)(std::sqrt(F) * (lds_scene ? 0.416 : 0.19) + 0.5);
-    g = std::max(1, std::min(g, lds_scene ? 16 : 4));
-    return std::min(g, n_frames);
-}
-
-// Whether a launch of n_frames with frames-per-item `group` runs in frame-split mode
-// (colour planes + k_accum_frames).  Register mode (group == n_frames: a lane owns whole
-// pixels, the running mean in registers) pulls one queue id per lane without batching, which
-// is right for long items.  But a launch of a few frames has items of a few segments, and
-// the chip-wide queue counter then throttles the kernel: one 1080p frame per launch (the
-// reference's one dispatch per displayed frame) took 3.2 ms of kernel time, against 0.5 ms
-// per frame in long launches.  In automatic mode such launches use the split path and its
-// batched reservations; pt_set_tuning key 5 >= n_frames still forces register mode.
-constexpr int kShortLaunch = 16;
-#ifndef PT_ORDER_EVERY
-#define PT_ORDER_EVERY 64
-#endif
-constexpr int kOrderEvery = PT_ORDER_EVERY;   // short launches per tile-order sort (enqueue_render)
+constexpr int kOrderEvery = 64;               // short launches per tile-order sort (enqueue_render)
 constexpr int kOrderFirst = 8;                // ... and before the first sort after an upload
 constexpr int kProbeFrames = 2, kProbeMin = 64;  // cold long renders: a sorted order after 2 frames
-static bool split_mode(const pt_ctx* c, int n_frames, int group) {
-    // the moments of the noise estimate are kept by the accumulate pass: with them on every
-    // launch is split, also whole-pixel items (tuning key 5 >= n_frames)
-    if (c->moments) return true;
-    if (group < n_frames) return true;
-    return c->group_force == 0 && n_frames <= kShortLaunch;
+
+// The launch planner's view of the context (pt_launch_plan.h).
+static ptl::Image plan_image(const pt_ctx* c) {
+    return {c->cfg.width, c->rows_local, c->n_tiles, c->cfg.rays_per_pixel, c->cfg.flags, c->n_cu, c->persist_blocks};
+}
+static ptl::State plan_state(const pt_ctx* c) { return {c->counting, c->moments != nullptr, c->aces_fuse}; }
+static ptl::LaunchPlan plan(const pt_ctx* c, int n_frames, bool graph) {
+    return ptl::plan_launch(c->sf, c->tun, plan_image(c), plan_state(c), n_frames, graph);
+}
+static int launch_frames(const pt_ctx* c, int n_frames) {
+    return ptl::launch_frames(c->sf, c->tun, plan_image(c), plan_state(c), n_frames);
 }
 
 // Grows the frame-split scratch to n_frames frame planes.  Earlier launches on the stream may
 // still read the old buffer, so the stream is drained first; a buffer a captured graph was
 // built with is handed to the graph (freed by drop_graph) instead of being freed under it.
-static int ensure_rgb(pt_ctx* c, int n_frames) {
-    size_t need = (size_t)std::max(c->rows_local, 1) * (size_t)c->cfg.width * (size_t)n_frames * 3 * sizeof(float);
+static int ensure_rgb(pt_ctx* c, size_t need) {
     if (need <= c->rgb_bytes) return PT_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->d_rgb && c->graph_exec && c->d_rgb == c->graph_rgb) c->graph_owned.push_back(c->d_rgb);
@@ -2400,7 +2279,7 @@ static int ensure_rgb(pt_ctx* c, int n_frames) {
 // created on first use.  The entry's buffer may still be read by the accumulate pass of the
 // last launch that used it, on any render stream, so a reallocation first drains the main
 // stream (every accumulate pass) and the render streams.
-static int ensure_slot(pt_ctx* c, int sl, int e, int n_frames) {
+static int ensure_slot(pt_ctx* c, int sl, int e, size_t need) {
     if (!c->rstream[sl]) HIPCHK(c, hipStreamCreateWithFlags(&c->rstream[sl], hipStreamNonBlocking));
     if (!c->ev_rdone[e]) {
         HIPCHK(c, hipEventCreateWithFlags(&c->ev_rdone[e], hipEventDisableTiming));
@@ -2408,7 +2287,6 @@ static int ensure_slot(pt_ctx* c, int sl, int e, int n_frames) {
         // the entry's queue heads start at zero; afterwards each accumulate pass re-zeroes them
         HIPCHK(c, hipMemset(c->d_work + kQueueSet * (1 + e), 0, kQueueSet * sizeof(unsigned)));
     }
-    const size_t need = (size_t)std::max(c->rows_local, 1) * (size_t)c->cfg.width * (size_t)n_frames * 3 * sizeof(float);
     if (need <= c->slot_rgb_bytes[e]) return PT_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int i = 0; i < kMaxSlots; i++)
@@ -2421,81 +2299,69 @@ static int ensure_slot(pt_ctx* c, int sl, int e, int n_frames) {
     return PT_OK;
 }
 
-// Queue ids are 32-bit: a launch's items * 64 plus what the resident waves can reserve past
-// the end stay below 2^32.  A wave reserves max(pull_batch, 64) ids per queue atomic and, once
-// the queue has run dry, at most two more reservations (the one that crossed the end and one
-// more; its lanes then finish), so the overshoot is at most (resident waves) * 2 *
-// max(pull_batch, 64), with at most persist_blocks * 4 resident waves (256-thread blocks) and
-// pull_batch at most 1024 (tuning key 4) or 256 (automatic).
-static unsigned long long id_limit(const pt_ctx* c) {
-    const unsigned long long pb = (unsigned long long)std::max(256, c->pull_batch);
-    const unsigned long long slack = (unsigned long long)c->persist_blocks * 4ull * 2ull * pb;
-    return (1ull << 32) - slack - (1ull << 20);
+// The main-stream scratch a launch of n_frames needs (none in register mode), in place before it.
+static int ensure_scratch(pt_ctx* c, int n_frames, bool graph) {
+    return ensure_rgb(c, ptl::scratch_bytes(plan(c, n_frames, graph), plan_image(c), n_frames));
 }
 
-// Frames of one launch for a render of n_frames: the largest count whose frame-split scratch
-// (12 B per pixel-frame) fits the context's budget and whose queue ids stay 32-bit.  A longer
-// render is issued as back-to-back launches of at most this many frames; only the first one
-// uses the caller's accumulate flag, so the result is that of n_frames dispatches (pt_api.h).
-static int launch_frames(const pt_ctx* c, int n_frames) {
-    const unsigned long long px = (unsigned long long)std::max(c->rows_local, 1) * (unsigned long long)c->cfg.width;
-    const unsigned long long tiles64 = (unsigned long long)std::max(c->n_tiles, 1) * 64ull;
-    int n = n_frames;
-    for (;;) {
-        const int g = plan_group(c, n);
-        if (!split_mode(c, n, g)) return n;    // register mode: no scratch, one group
-        // one frame per launch always runs, even when its scratch exceeds the budget (so n
-        // strictly decreases to at most 1: the loop ends)
-        const unsigned long long by_budget = std::max(1ull, c->scratch_budget / (px * 12ull));
-        const unsigned long long ng = (unsigned long long)((n + g - 1) / g);
-        const unsigned long long lim = id_limit(c);
-        const unsigned long long by_ids = (lim / tiles64) * (unsigned long long)g;
-        if (((unsigned long long)n <= by_budget && ng * tiles64 < lim) || n == 1) return n;
-        const unsigned long long m = std::min<unsigned long long>({(unsigned long long)n - 1, by_budget, by_ids});
-        n = (int)std::max<unsigned long long>(m, 1ull);
-    }
+// k_render_sm by its template arguments: key and kernel from the same pt_render_kernels.h line.
+struct RenderKernel { ptl::KernelKey key; void (*fn)(KParams); };
+#define PT_X(C, L, MW, M, S, P, NT, W) {{C, L, MW, M, S, P, NT, W}, k_render_sm<C, L, MW, M, S, P, NT, W>},
+static const RenderKernel kRenderKernels[] = {PT_RENDER_KERNELS(PT_X)};
+#undef PT_X
+static const RenderKernel* find_kernel(const ptl::KernelKey& key) {
+    for (const RenderKernel& k : kRenderKernels)
+        if (k.key == key) return &k;
+    return nullptr;
+}
+typedef void (*KParamsKernel)(KParams);
+static KParamsKernel accum_kernel(const ptl::LaunchPlan& pl) {   // the accumulate pass of a split launch
+    if (pl.accum_long) return pl.accum_moments ? k_accum_frames<kAccumPixLong, kAccumFramesLong, true>
+                                               : k_accum_frames<kAccumPixLong, kAccumFramesLong>;
+    return pl.accum_moments ? k_accum_frames<kAccumPix, 1, true> : k_accum_frames<kAccumPix, 1>;
 }
 
-// Whether the state-machine kernel's LDS walk culls: the tree qualifies
-// (walk_nested), key 15 leaves it on, nothing is counted, and the sink image (32 B per node
-// beside the 16 N octant records) costs no resident block -- a scene whose copy just fits
-// mw blocks per CU in 160 KiB would otherwise lose a block per CU, far more than the walk
-// gains (+7%).
-static bool cons_walk_on(const pt_ctx* c) {
-    if (!c->walk_nested || c->cons_off || c->counting) return false;
-    const size_t mw = (size_t)(c->minw ? c->minw : 7);
-    const auto blocks = [mw](size_t b) { return b ? std::min(mw, (size_t)(160 * 1024) / b) : mw; };
-    return blocks(c->lds_bytes_sk) >= blocks(c->lds_bytes);
+// The image half of the kernel parameters (every kernel that takes KParams reads these).
+static void fill_image(KParams& p, const pt_ctx* c) {
+    p.W = c->cfg.width, p.H = c->cfg.height;
+    p.row0 = c->cfg.rank, p.row_stride = c->cfg.world, p.rows_local = c->rows_local;
+    p.x_limit = (c->cfg.flags & PT_FLAG_REF_DISPATCH) ? (p.W / 10) * 10 : p.W;
+    p.y_limit = (c->cfg.flags & PT_FLAG_REF_DISPATCH) ? (p.H / 10) * 10 : p.H;
 }
 
-// Whether a global-memory launch walks the wide tree: the scene has one
-// (a nested tree), it lies inside the scene half of the exact-reciprocal guard (otherwise no
-// lane could use it), tuning key 16 leaves it on, nothing is counted, and the occupancy is
-// one the wide instantiations cover (5-7 waves per SIMD; automatic 6).
-constexpr int kWideTopMax = 1 << 14;   // wide records staged in LDS: what the block's LDS share holds
-#ifndef PT_WIDE_THREADS
-#define PT_WIDE_THREADS 256
-#endif
-constexpr int kWideThreadsAuto = PT_WIDE_THREADS;   // threads per block of the wide walk (tuning key 17)
-static bool wide_walk_on(const pt_ctx* c) {
-    return c->wide_ok && c->scene_fast && !c->wide_off && !c->counting && c->minw != 8;
-}
-
-// Threads per workgroup of the state-machine kernel on an LDS-staged scene of `lds` bytes:
-// the k = 1..4 waves per SIMD per workgroup that make the most resident waves, min(floor(160
-// KiB / lds), floor(7 / k)) * k (7 waves per SIMD is the kernel's register budget), the
-// narrowest on a tie: 256 threads down to a 23 KiB copy, then 512 / 768 / 1024 (6, 6, 4 waves
-// per SIMD at 32 / 54 / 160 KiB).  The wide instantiations are the default configuration's (non-counting, one ray
-// per pixel, automatic occupancy); other launches keep 256 threads.
-static int lds_threads(const pt_ctx* c, size_t lds) {
-    if (!PT_LDS_WIDE || c->counting || c->minw || c->cfg.rays_per_pixel > 1 || !lds) return 256;
-    const int per_cu = (int)((size_t)(160 * 1024) / lds);     // copies resident per CU
-    int best_k = 1, best = 0;
-    for (int k = 1; k <= 4; k++) {      // k waves per SIMD per workgroup, at most 7 per SIMD
-        const int waves = std::min(per_cu, 7 / k) * k;
-        if (waves > best) { best = waves; best_k = k; }
-    }
-    return 256 * best_k;
+// The kernel parameters of a launch, from the context and its plan (scratch, queue head and
+// the accumulate pass's outputs are the caller's).
+static KParams fill_params(const pt_ctx* c, const ptl::LaunchPlan& pl, int frame_first, int n_frames, int acc_first,
+                           const int* frame_dev, int frame_offset) {
+    KParams p;
+    std::memset(&p, 0, sizeof(p));
+    // the wide walk reads the node / triangle arrays numbered by its index, and its records
+    p.sc = {pl.wide ? c->d_nodesw : c->d_nodes, c->d_walk_lds, c->d_walk_sk, pl.wide ? c->d_trisw : c->d_tris,
+            c->d_mats, c->d_spheres, pl.wide ? c->d_wrec : nullptr, pl.wide ? c->d_wlbox : nullptr,
+            c->sf.n_nodes, c->sf.n_spheres};
+    if (pl.wide) std::memcpy(p.wide_cw, c->sf.wide_cw, sizeof(p.wide_cw));
+    fill_image(p, c);
+    p.rW = 1.0f / (float)p.W, p.fW = (float)p.W, p.fH = (float)p.H, p.rH = 1.0f / (float)p.H;
+    p.accum = c->accum;
+    std::memcpy(p.cam, c->cam, sizeof(p.cam));
+    p.frame_first = frame_first, p.n_frames = n_frames, p.acc_first = acc_first;
+    p.frame_dev = frame_dev, p.frame_offset = frame_offset;
+    p.max_bounce = c->cfg.max_bounce, p.mode = c->cfg.display_mode, p.flags = c->cfg.flags, p.rpp = c->cfg.rays_per_pixel;
+    p.counters = c->d_counters, p.work_counter = c->d_work;
+    // scene facts
+    p.n_slots = c->sf.n_slots, p.walk_np = c->sf.walk_np, p.n_mats = c->sf.n_mats, p.scene_fast = c->sf.scene_fast;
+    std::memcpy(p.cons_m, c->sf.cons_m, sizeof(p.cons_m));
+    std::memcpy(p.root_box, c->sf.root_box, sizeof(p.root_box));
+    p.root_child = c->sf.root_child;
+    // the plan
+    p.n_top = pl.n_top, p.wide_top = pl.wide_top, p.shade_lds = pl.shade_lds;
+    p.cons_walk = pl.cons_walk, p.leaf_cert = pl.leaf_cert;
+    p.leaf_thresh = pl.leaf_thresh, p.shade_thresh = pl.shade_thresh, p.trav_floor = pl.trav_floor;
+    p.compact_max = c->tun.compact_max;
+    p.group = pl.group, p.pull_batch = pl.pull_batch, p.grp_magic = pl.grp_magic;
+    p.tile_perm = c->d_tile_perm, p.tile_shift = c->tile_shift;
+    p.tile_cost = (c->tun.adaptive && !c->counting) ? c->d_tile_cost : nullptr;
+    return p;
 }
 
 // Enqueues one render launch (work-queue reset + kernel) on the context stream.  With
@@ -2503,270 +2369,63 @@ static int lds_threads(const pt_ctx* c, size_t lds) {
 static int enqueue_render(pt_ctx* c, int frame_first, int n_frames, int acc_first, const int* frame_dev,
                           int frame_offset, bool force_sort = false) {
     c->stage_ok = false;    // this launch changes the image: rgba8 holds its view only if written below
-    KParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.sc.nodes = c->d_nodes;
-    p.sc.walk_lds = c->d_walk_lds;
-    p.sc.tris = c->d_tris;
-    p.sc.mats = c->d_mats;
-    p.sc.spheres = c->d_spheres;
-    p.sc.n_nodes = c->n_nodes;
-    p.sc.n_spheres = c->n_spheres;
-    p.accum = c->accum;
-    std::memcpy(p.cam, c->cam, sizeof(p.cam));
-    p.W = c->cfg.width;
-    p.H = c->cfg.height;
-    p.row0 = c->cfg.rank;
-    p.row_stride = c->cfg.world;
-    p.rows_local = c->rows_local;
-    p.x_limit = (c->cfg.flags & PT_FLAG_REF_DISPATCH) ? (p.W / 10) * 10 : p.W;
-    p.y_limit = (c->cfg.flags & PT_FLAG_REF_DISPATCH) ? (p.H / 10) * 10 : p.H;
-    p.frame_first = frame_first;
-    p.n_frames = n_frames;
-    p.acc_first = acc_first;
-    p.frame_dev = frame_dev;
-    p.frame_offset = frame_offset;
-    p.max_bounce = c->cfg.max_bounce;
-    p.mode = c->cfg.display_mode;
-    p.flags = c->cfg.flags;
-    p.rpp = c->cfg.rays_per_pixel;
-    p.counters = c->d_counters;
-    p.work_counter = c->d_work;
-    p.n_slots = c->n_slots;
-    p.n_top = c->n_top;
-    p.walk_np = c->walk_np;
-    p.n_mats = c->n_mats;
-    p.scene_fast = c->scene_fast;
-    p.cons_walk = cons_walk_on(c);
-    // the certificate stands on hit_triangle's plane distance: not in Moller-Trumbore mode.
-    // The wide walk only: on the LDS culling walk (C2, VALU-bound, the box re-read from LDS)
-    // its ~40 VALU per leaf phase cost more than the re-test (-1.9%, same-process A/B r05c)
-    p.leaf_cert = c->leaf_cert_ok && !c->cert_off && !(c->cfg.flags & PT_FLAG_MOLLER_TRUMBORE);
-    p.sc.walk_sk = c->d_walk_sk;
-    std::memcpy(p.cons_m, c->cons_m, sizeof(p.cons_m));
-    std::memcpy(p.root_box, c->root_box, sizeof(p.root_box));
-    p.root_child = c->root_child;
-    {
-        bool lds_scene = lds_staged(c);
-        p.leaf_thresh = c->leaf_thresh ? c->leaf_thresh : (lds_scene ? 52 : 20);
-        p.shade_thresh = c->shade_thresh ? c->shade_thresh : (lds_scene ? 44 : 24);
-        // walk floor: 5 for the small LDS scenes (C2), 8 for the wide-workgroup ones (keysweep
-        // on the 150 / 380-triangle stand-ins: +0.8% / +1.2% over 5), 6 for global memory
-        p.trav_floor = c->trav_floor ? c->trav_floor : (lds_scene ? (c->lds_bytes > kLdsSceneSmall ? 8 : 5) : 6);
-        p.compact_max = c->compact_max;
-    }
-    p.rW = 1.0f / (float)p.W;
-    p.fW = (float)p.W;
-    p.fH = (float)p.H;
-    p.rH = 1.0f / (float)p.H;
-    p.group = plan_group(c, n_frames);
-    // queue ids reserved per queue atomic: on an LDS-staged scene an item of one or two
-    // frames is a few short segments, and the chip-wide counter then limits the launch (one
-    // 1080p Cornell frame per launch: 1.14 ms kernel time with 32 ids per reservation, 0.97
-    // with 128; 4K 3.44 -> 2.64 ms; 4-frame launches 0.83 -> 0.62 ms per frame).  A wave
-    // that reserves more ids than it soon needs lengthens the launch tail instead, so longer
-    // items and the global-memory scenes' long segments keep 32 (C3 stand-in, one frame per
-    // launch: 3.19 ms with 32, 3.63 with 128).  With overlapped one-frame launches (2 slots)
-    // 256 ids beat 128 (0.594 vs 0.603 ms per 1080p frame; 64: 0.689).  Tuning key 4 overrides.
-    //
-    // Otherwise (round 3 sweep, same process) the best reservation follows the queue ids a
-    // resident wave takes over the launch, I, and the frames per item, g: about I / (8 g),
-    // between 32 and 256.  Global-memory scenes (C3 stand-in): one-frame launches best at 48
-    // (+4% over 32), 4-frame 128 (+3.8%), 8-frame 64 (+1.9%), 16-frame 32, 32-frame 64 (+1%),
-    // 64-frame 128 (+1.3%), 256-frame 192-256 (+2.2%; C4 +2.1%); C2's 1024-frame launch 128
-    // (+0.9%).  Fewer ids per wave than that make the queue atomic's round trip frequent;
-    // more leave the last waves holding a long reservation in the launch tail.
-    {
-        const bool lds_items = lds_staged(c);
-        const double waves = (double)c->n_cu * 4.0 * (lds_items ? 7.0 : 6.0);
-        const double ids = (double)c->n_tiles * (double)((n_frames + p.group - 1) / p.group) * 64.0;
-        const int fit = 16 * (int)(ids / std::max(waves, 1.0) / (8.0 * p.group) / 16.0 + 0.5);
-        const int auto_batch = std::max((int)kPullBatch, std::min(256, fit));
-        p.pull_batch = c->pull_batch ? c->pull_batch
-                                     : (lds_items && p.group <= 2 ? (p.group == 1 ? 256 : 64) : auto_batch);
-    }
-    {   // exact item / n_groups by ceil(2^32 / n_groups) when item * n_groups < 2^32 for every
-        // item (then floor(item * m / 2^32) = floor(item / n_groups)), else the division
-        const unsigned long long ng = (unsigned long long)((n_frames + p.group - 1) / p.group);
-        const unsigned long long items = (unsigned long long)c->n_tiles * ng;
-        p.grp_magic = (ng > 1 && items * ng < (1ull << 32)) ? (unsigned)(((1ull << 32) + ng - 1) / ng) : 0u;
-    }
-    // Overlapped short launches: a short frame-split render (the reference's one dispatch per
-    // displayed frame, ogl_path_trace.h:160-204) ends in a tail of nearly empty waves.  Its
-    // render kernel runs on overlap slot `sl` (own stream, colour scratch and queue counter)
-    // so the next render's waves fill the CUs that this one's tail frees; the accumulate pass
-    // stays on the main stream, in frame order (the running mean, :548-551).  Dependencies:
-    // the slot's scratch is reused only after the accumulate pass that read it (ev_adone), and
-    // a render never overlaps a tile-order sort (ev_sort; the sort runs on the main stream,
-    // which has waited for every earlier render).  Not for captured graphs or counting.
-    const bool overlap = c->overlap_slots > 1 && !frame_dev && !c->counting && n_frames <= kShortLaunch &&
-                         split_mode(c, n_frames, p.group);
+    const ptl::LaunchPlan pl = plan(c, n_frames, frame_dev != nullptr);
+    KParams p = fill_params(c, pl, frame_first, n_frames, acc_first, frame_dev, frame_offset);
+    // Overlapped short launches (the plan's `overlap`): the render kernel runs on overlap slot
+    // `sl` (own stream, colour scratch and queue counter); the accumulate pass stays on the
+    // main stream, in frame order (the running mean, :548-551).  Dependencies: the slot's
+    // scratch is reused only after the accumulate pass that read it (ev_adone), and a render
+    // never overlaps a tile-order sort (ev_fence; the sort runs on the main stream, which has
+    // waited for every earlier render).
+    const size_t scratch = ptl::scratch_bytes(pl, plan_image(c), n_frames);
     const int sl = c->slot;
-    const int ring = kRingMult * c->overlap_slots;
+    const int ring = kRingMult * c->tun.overlap_slots;
     const int re = c->ring % ring;       // this launch's scratch-ring entry
     hipStream_t rs = c->stream;
     unsigned* work = c->d_work;
-    if (overlap) {
-        int rc = ensure_slot(c, sl, re, n_frames);
+    if (pl.overlap) {
+        int rc = ensure_slot(c, sl, re, scratch);
         if (rc) return rc;
         rs = c->rstream[sl];
         work = c->d_work + kQueueSet * (1 + re);
         p.rgb = c->slot_rgb[re];
         p.work_counter = work;
-        c->slot = (sl + 1) % c->overlap_slots;
+        c->slot = (sl + 1) % c->tun.overlap_slots;
         c->ring = (re + 1) % ring;
-    } else if (split_mode(c, n_frames, p.group)) {
-        int rc = ensure_rgb(c, n_frames);
+    } else if (pl.split) {
+        int rc = ensure_rgb(c, scratch);
         if (rc) return rc;
         p.rgb = c->d_rgb;
     }
-    p.tile_perm = c->d_tile_perm;
-    p.tile_shift = c->tile_shift;
-    p.tile_cost = (c->adaptive && !c->counting) ? c->d_tile_cost : nullptr;
     if (c->rows_local == 0) return PT_OK;
-    // variants: 0 state machine (default), 3 = 0 with the scene forced to stay in global memory
-    const int variant = c->variant;
-    const bool use_lds = variant == 0 && lds_staged(c);
-    // the global-memory walk of a nested tree takes the wide tree (pt_wide.h) unless tuning
-    // key 16 turns it off; counting builds keep the binary walk (their counts are the
-    // reference's), and so do occupancy overrides other than 6 waves per SIMD
-    const bool use_wide = !use_lds && wide_walk_on(c);
-    p.leaf_cert = p.leaf_cert && use_wide;
-    if (use_wide) {
-        p.sc.nodes = c->d_nodesw;
-        p.sc.tris = c->d_trisw;
-        p.sc.wrec = c->d_wrec;
-        p.sc.wlbox = c->d_wlbox;
-        std::memcpy(p.wide_cw, c->wide_cw, sizeof(p.wide_cw));
+    const RenderKernel* kernel = find_kernel(pl.key);
+    if (!kernel) {
+        const ptl::KernelKey& k = pl.key;
+        char key[96];
+        std::snprintf(key, sizeof key, "<%d,%d,%d,%d,%d,%d,%d,%d>", k.count, k.lds, k.minw, k.multi, k.split, k.padn, k.nt, k.wide);
+        return fail(c, PT_E_STATE, std::string("no k_render_sm instantiation for the launch key ") + key);
     }
-    if (overlap) {
+    if (pl.overlap) {
         if (c->adone_rec[re]) HIPCHK(c, hipStreamWaitEvent(rs, c->ev_adone[re], 0));
         if (c->fence_rec) HIPCHK(c, hipStreamWaitEvent(rs, c->ev_fence, 0));
     }
     // an overlap slot's heads were zeroed by the accumulate pass of its last render (or at
     // the slot's creation)
-    if (overlap) p.reset_work = work;
+    if (pl.overlap) p.reset_work = work;
     else HIPCHK(c, hipMemsetAsync(work, 0, kQueueSet * sizeof(unsigned), rs));
-    {
-        // persistent grid: enough resident waves to fill every SIMD; surplus blocks find the
-        // queue empty and exit.  Never more blocks than 8x8 tiles (64 lanes per tile).
-        size_t lds = use_lds ? (p.cons_walk ? c->lds_bytes_sk : c->lds_bytes) : 0;
-        unsigned tiles = (unsigned)c->n_tiles;
-        unsigned items = tiles * (unsigned)((n_frames + p.group - 1) / p.group);   // 64-lane items
-        // the wide walk's workgroup: wider ones share one LDS copy of more top records
-        // (tuning key 17); raysPerPixel > 1 keeps 256 threads
-        const int wide_nt = (use_wide && p.rpp == 1) ? (c->wide_threads ? c->wide_threads : kWideThreadsAuto) : 256;
-        const int nt = (variant == 0 && use_lds) ? lds_threads(c, lds) : (use_wide ? wide_nt : 256);
-        const unsigned wpb = (unsigned)nt / 64u;                                    // waves per block
-        unsigned blocks = std::min<unsigned>(c->persist_blocks * 256u / (unsigned)nt,
-                                             std::max(1u, (items + wpb - 1) / wpb));
-        dim3 grid(blocks);
-        // occupancy: 7 waves/SIMD for LDS scenes (72 VGPRs, a few spilled: +0.8% on C2 over
-        // 6, which was +5% over 5; 8 spills 20+ and loses 7%), 6 for global-memory scenes (7
-        // leaves fewer top nodes per block in LDS: -6% on the C3 stand-in)
-        const int mw = c->minw ? c->minw : (use_lds ? 7 : 6);
-        // Overlapped short renders (tuning key 18): at most this many 256-thread blocks per CU
-        // (automatic: one fewer than resident, two fewer with 3+ render slots), so the accumulate pass and the ACES view of the
-        // previous render find free slots beside the next render instead of waiting for its
-        // blocks to retire.  1080p Cornell, one frame per dispatch (tools/interactive_fps.py):
-        // 0.534 -> 0.514 ms per frame, and 0.68 -> 0.55-0.58 with every frame shown
-        // (pt_present, lag 2); accumulate pass 243 -> 103 us.  Round 5, 3 slots, 600-800 frames
-        // (profiles/ab/r05i_interactive_sweep.json, r05j_*): render only, 2 / 3 / 4 / 5 blocks
-        // per CU 0.513 / 0.473 / 0.537 / 0.493 ms per frame; every frame presented at lag 2, 3
-        // blocks 0.55-0.62 against 0.530 at 5.  So 3 slots take 3 blocks per CU, or 5 when the
-        // caller presented after the previous render (aces_fuse).
-        if (overlap && nt == 256) {
-            const int bpc = c->overlap_bpc ? c->overlap_bpc
-                          : c->overlap_slots >= 3 ? (c->aces_fuse ? std::max(1, mw - 2) : 3)
-                                                  : std::max(1, mw - 1);
-            grid.x = std::min<unsigned>(grid.x, (unsigned)(bpc * c->n_cu));
+    hipLaunchKernelGGL(kernel->fn, dim3(pl.blocks), dim3((unsigned)kernel->key.nt), pl.dyn_lds_bytes, rs, p);
+    if (pl.split) {
+        if (pl.overlap) {
+            HIPCHK(c, hipEventRecord(c->ev_rdone[re], rs));
+            HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_rdone[re], 0));
         }
-        // global scene: the top nodes staged per block, at most what mw blocks per CU fit in
-        // its 160 KiB of LDS (the first K of the breadth-first numbering, any K <= n_top)
-        if (mw > 6) p.n_top = std::min(c->n_top, 160 * 1024 / mw / 32 - 8);
-        // materials + spheres beside the top nodes when they are small (<= 4 KiB)
-        const size_t shade_bytes = (size_t)(3 * c->n_mats + 2 * c->n_spheres) * sizeof(float4);
-        p.shade_lds = shade_bytes <= 4096;
-        if (use_wide) {   // top records: 48 B each, within the block's share of the CU's LDS
-            // (256-thread blocks: one per resident wave per SIMD, the instantiation's 5-7; the
-            // raysPerPixel > 1 one is built for 6)
-            const size_t blocks_cu = wide_nt == 1024 ? 1
-                                   : (wide_nt == 256 ? (size_t)(p.rpp > 1 ? 6 : std::min(std::max(mw, 5), 7))
-                                                     : (size_t)(6 * 256 / wide_nt));
-            // (1 KiB below the even share: the allocation granule must not cost a block per CU)
-            p.wide_top = (int)std::min<size_t>({(size_t)c->n_wide, (size_t)kWideTopMax,
-                                                ((size_t)160 * 1024 / blocks_cu - (p.shade_lds ? shade_bytes : 0) - 1024) / 48});
-        }
-        const size_t top_lds = use_wide ? (size_t)p.wide_top * 3 * sizeof(float4) + (p.shade_lds ? shade_bytes : 0)
-                                        : (size_t)p.n_top * 2 * sizeof(float4) + (p.shade_lds ? shade_bytes : 0);
-#define PT_LAUNCH_SM(L, M)                                                                                \
-    if (c->counting && p.rgb) hipLaunchKernelGGL((k_render_sm<true, L, 5, M, true>), grid, dim3(256), L ? lds : top_lds, rs, p); \
-    else if (c->counting) hipLaunchKernelGGL((k_render_sm<true, L, 5, M, false>), grid, dim3(256), L ? lds : top_lds, rs, p); \
-    else if (p.rgb && mw == 8 && !M) hipLaunchKernelGGL((k_render_sm<false, L, 8, false, true>), grid, dim3(256), L ? lds : top_lds, rs, p); \
-    else if (p.rgb && mw == 7 && !M && L && c->walk_np == kPadNodes) hipLaunchKernelGGL((k_render_sm<false, true, 7, false, true, true>), grid, dim3(256), lds, rs, p); \
-    else if (p.rgb && mw == 7 && !M) hipLaunchKernelGGL((k_render_sm<false, L, 7, false, true>), grid, dim3(256), L ? lds : top_lds, rs, p); \
-    else if (p.rgb && mw >= 6) hipLaunchKernelGGL((k_render_sm<false, L, 6, M, true>), grid, dim3(256), L ? lds : top_lds, rs, p); \
-    else if (p.rgb) hipLaunchKernelGGL((k_render_sm<false, L, 5, M, true>), grid, dim3(256), L ? lds : top_lds, rs, p); \
-    else if (mw >= 6) hipLaunchKernelGGL((k_render_sm<false, L, 6, M, false>), grid, dim3(256), L ? lds : top_lds, rs, p); \
-    else hipLaunchKernelGGL((k_render_sm<false, L, 5, M, false>), grid, dim3(256), L ? lds : top_lds, rs, p);
-#define PT_LAUNCH_WIDE(NT, MW)                                                                                \
-    if (p.rgb) hipLaunchKernelGGL((k_render_sm<false, true, MW, false, true, false, NT>), grid, dim3(NT), lds, rs, p); \
-    else hipLaunchKernelGGL((k_render_sm<false, true, MW, false, false, false, NT>), grid, dim3(NT), lds, rs, p);
-        // lds_threads: LDS scene, variant 0, one ray per pixel; the register budget of the
-        // waves that are resident (6, 6, 4 per SIMD), not of 7
-        if (use_wide) {
-#define PT_LAUNCH_WIDE_G(NT, MW)                                                                              \
-    if (p.rgb) hipLaunchKernelGGL((k_render_sm<false, false, MW, false, true, false, NT, true>), grid, dim3(NT), top_lds, rs, p); \
-    else hipLaunchKernelGGL((k_render_sm<false, false, MW, false, false, false, NT, true>), grid, dim3(NT), top_lds, rs, p);
-            if (p.rgb && p.rpp > 1) hipLaunchKernelGGL((k_render_sm<false, false, 6, true, true, false, 256, true>), grid, dim3(256), top_lds, rs, p);
-            else if (p.rpp > 1) hipLaunchKernelGGL((k_render_sm<false, false, 6, true, false, false, 256, true>), grid, dim3(256), top_lds, rs, p);
-            else if (nt == 512) { PT_LAUNCH_WIDE_G(512, 6) }
-            else if (nt == 768) { PT_LAUNCH_WIDE_G(768, 6) }
-            else if (nt == 1024) { PT_LAUNCH_WIDE_G(1024, 4) }
-            else if (mw == 5) { PT_LAUNCH_WIDE_G(256, 5) }
-            else if (mw == 7) { PT_LAUNCH_WIDE_G(256, 7) }
-            else { PT_LAUNCH_WIDE_G(256, 6) }
-#undef PT_LAUNCH_WIDE_G
-        } else if (nt > 256) {
-            if (nt == 512) { PT_LAUNCH_WIDE(512, 6) }
-            else if (nt == 768) { PT_LAUNCH_WIDE(768, 6) }
-            else { PT_LAUNCH_WIDE(1024, 4) }
-#undef PT_LAUNCH_WIDE
-        } else {
-            bool multi = p.rpp > 1;
-            if (use_lds && multi) { PT_LAUNCH_SM(true, true) }
-            else if (use_lds) { PT_LAUNCH_SM(true, false) }
-            else if (multi) { PT_LAUNCH_SM(false, true) }
-            else { PT_LAUNCH_SM(false, false) }
-#undef PT_LAUNCH_SM
-        }
-        if (p.rgb) {
-            if (overlap) {
-                HIPCHK(c, hipEventRecord(c->ev_rdone[re], rs));
-                HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_rdone[re], 0));
-            }
-            long long px = (long long)c->rows_local * p.W;
-            // a presenting caller's view of the new image, written by the same pass (not inside
-            // a captured graph: its replays are not followed by pt_present_begin's check)
-            p.aces_out = (c->aces_fuse && !frame_dev) ? c->rgba8 : nullptr;
-            c->stage_ok = p.aces_out != nullptr;
-            p.moments = c->moments;
-            const dim3 grid_long((unsigned)((px + 256 * kAccumPixLong - 1) / (256 * kAccumPixLong)));
-            const dim3 grid_short((unsigned)((px + 256 * kAccumPix - 1) / (256 * kAccumPix)));
-            if (n_frames > kShortLaunch && p.moments)
-                hipLaunchKernelGGL((k_accum_frames<kAccumPixLong, kAccumFramesLong, true>), grid_long, dim3(256), 0,
-                                   c->stream, p);
-            else if (n_frames > kShortLaunch)
-                hipLaunchKernelGGL((k_accum_frames<kAccumPixLong, kAccumFramesLong>), grid_long, dim3(256), 0,
-                                   c->stream, p);
-            else if (p.moments)
-                hipLaunchKernelGGL((k_accum_frames<kAccumPix, 1, true>), grid_short, dim3(256), 0, c->stream, p);
-            else
-                hipLaunchKernelGGL((k_accum_frames<kAccumPix, 1>), grid_short, dim3(256), 0, c->stream, p);
-            if (overlap) {
-                HIPCHK(c, hipEventRecord(c->ev_adone[re], c->stream));
-                c->adone_rec[re] = true;
-            }
+        p.aces_out = pl.aces_out ? c->rgba8 : nullptr;
+        c->stage_ok = pl.aces_out;
+        p.moments = c->moments;
+        hipLaunchKernelGGL(accum_kernel(pl), dim3(pl.accum_blocks), dim3(256), 0, c->stream, p);
+        if (pl.overlap) {
+            HIPCHK(c, hipEventRecord(c->ev_adone[re], c->stream));
+            c->adone_rec[re] = true;
         }
     }
     // The queue order is recomputed from the accumulated tile costs after every long launch,
@@ -2814,16 +2473,13 @@ static int enqueue_frames(pt_ctx* c, int frame_first, int n_frames, int acc_firs
     // upload) would run in raster order.  Its first kProbeFrames frames go first as a short
     // launch whose tile costs are sorted at once, so the remaining frames already run most-
     // expensive-tile-first; the continuation accumulates, so the image is unchanged.
-    if (!frame_dev && c->adaptive && !c->counting && !c->order_sorted && n_frames >= kProbeMin) {
+    if (!frame_dev && c->tun.adaptive && !c->counting && !c->order_sorted && n_frames >= kProbeMin) {
         // the scratch for the launch this render would have been: the next identical render
         // then finds it in place instead of freeing and mapping ~25 GB (1.5 s measured on one
         // box) in front of its kernel
-        const int full = launch_frames(c, n_frames);
-        if (split_mode(c, full, plan_group(c, full))) {
-            int rc = ensure_rgb(c, full);
-            if (rc) return rc;
-        }
-        int rc = enqueue_render(c, frame_first, kProbeFrames, acc_first, nullptr, 0, true);
+        int rc = ensure_scratch(c, launch_frames(c, n_frames), false);
+        if (rc) return rc;
+        rc = enqueue_render(c, frame_first, kProbeFrames, acc_first, nullptr, 0, true);
         if (rc) return rc;
         frame_first += kProbeFrames;
         n_frames -= kProbeFrames;
@@ -2896,11 +2552,8 @@ int pt_progressive_setup(pt_ctx* c, int frames_per_launch, int launches_per_repl
     }
     if (!c->d_frame) HIPCHK(c, hipMalloc(&c->d_frame, 64));
     {   // no allocation inside the capture: the scratch of the largest sub-launch first
-        const int n = launch_frames(c, frames_per_launch);
-        if (split_mode(c, n, plan_group(c, n))) {
-            int rc0 = ensure_rgb(c, n);
-            if (rc0) return rc0;
-        }
+        int rc0 = ensure_scratch(c, launch_frames(c, frames_per_launch), true);
+        if (rc0) return rc0;
     }
     HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
     int rc = PT_OK;
@@ -2941,15 +2594,10 @@ int pt_progressive_run(pt_ctx* c, int replays) {
     if (replays <= 0) return fail(c, PT_E_ARG, "replays must be > 0");
     HIPCHK(c, hipSetDevice(c->cfg.device));
     hipEvent_t ev[2];
-    for (int i = 0; i < 2; i++) {
-        if (c->ev_free.empty()) {
-            HIPCHK(c, hipEventCreate(&ev[i]));
-        } else {
-            ev[i] = c->ev_free.back();
-            c->ev_free.pop_back();
-        }
+    {
+        int rc = take_events(c, ev);
+        if (rc) return rc;
     }
-    c->ev_pending.emplace_back(ev[0], ev[1]);
     HIPCHK(c, hipEventRecord(ev[0], c->stream));
     for (int r = 0; r < replays; r++) HIPCHK(c, hipGraphLaunch(c->graph_exec, c->stream));
     if (c->moments) c->mom_frames += replays * c->graph_frames;
@@ -3013,10 +2661,10 @@ int pt__scene_replicate_layout(pt_ctx* dst, const pt_ctx* src, void* dptr[10], c
     HIPCHK(dst, hipStreamSynchronize(dst->stream));
     drop_graph(dst);
     free_scene(dst);
-    const size_t nd = 2 * (size_t)std::max(src->n_nodes, 1), nt = 8 * (size_t)std::max(src->n_slots / 2, 1);
-    const size_t nm = 3 * (size_t)std::max(src->n_mats, 1), ns = 2 * (size_t)std::max(src->n_spheres, 1);
-    const size_t nw = 16 * (size_t)src->walk_np, nk = src->d_walk_sk ? 18 * (size_t)src->walk_np : 0;
-    const size_t ni = src->wide_ok ? (size_t)src->n_wide : 0;   // the wide walk's arrays (pt_wide.h)
+    const size_t nd = 2 * (size_t)std::max(src->sf.n_nodes, 1), nt = 8 * (size_t)std::max(src->sf.n_slots / 2, 1);
+    const size_t nm = 3 * (size_t)std::max(src->sf.n_mats, 1), ns = 2 * (size_t)std::max(src->sf.n_spheres, 1);
+    const size_t nw = 16 * (size_t)src->sf.walk_np, nk = src->d_walk_sk ? 18 * (size_t)src->sf.walk_np : 0;
+    const size_t ni = src->sf.wide_ok ? (size_t)src->sf.n_wide : 0;   // the wide walk's arrays (pt_wide.h)
     const size_t sz[10] = {nd, nt, nm, ns, nw, nk, kWideStride * ni, 2 * ni, ni ? nd : 0, 8 * ni};
     float4** mine[10] = {&dst->d_nodes, &dst->d_tris, &dst->d_mats, &dst->d_spheres, &dst->d_walk_lds, &dst->d_walk_sk,
                          &dst->d_wrec, &dst->d_wlbox, &dst->d_nodesw, &dst->d_trisw};
@@ -3028,23 +2676,7 @@ int pt__scene_replicate_layout(pt_ctx* dst, const pt_ctx* src, void* dptr[10], c
         if (sz[i]) HIPCHK(dst, hipMalloc(mine[i], bytes[i]));
         dptr[i] = *mine[i];
     }
-    dst->n_nodes = src->n_nodes;
-    dst->n_spheres = src->n_spheres;
-    dst->n_mats = src->n_mats;
-    dst->n_slots = src->n_slots;
-    dst->n_top = src->n_top;
-    dst->scene_fast = src->scene_fast;
-    dst->walk_nested = src->walk_nested;
-    std::memcpy(dst->cons_m, src->cons_m, sizeof(dst->cons_m));
-    dst->wide_ok = src->wide_ok;
-    dst->leaf_cert_ok = src->leaf_cert_ok;
-    dst->n_wide = src->n_wide;
-    std::memcpy(dst->wide_cw, src->wide_cw, sizeof(dst->wide_cw));
-    dst->walk_np = src->walk_np;
-    dst->lds_bytes = src->lds_bytes;
-    dst->lds_bytes_sk = src->lds_bytes_sk;
-    std::memcpy(dst->root_box, src->root_box, sizeof(dst->root_box));
-    dst->root_child = src->root_child;
+    dst->sf = src->sf;
     dst->order_sorted = false;
     dst->order_skip = 0;
     // scene_ok stays false until the caller has filled the buffers (pt__scene_set_ready): a
@@ -3149,13 +2781,7 @@ int pt_noise(pt_ctx* c, float target, pt_noise_stats* out) {
     if (px > 0) {
         KParams p;
         std::memset(&p, 0, sizeof(p));
-        p.W = c->cfg.width;
-        p.H = c->cfg.height;
-        p.row0 = c->cfg.rank;
-        p.row_stride = c->cfg.world;
-        p.rows_local = c->rows_local;
-        p.x_limit = (c->cfg.flags & PT_FLAG_REF_DISPATCH) ? (p.W / 10) * 10 : p.W;
-        p.y_limit = (c->cfg.flags & PT_FLAG_REF_DISPATCH) ? (p.H / 10) * 10 : p.H;
+        fill_image(p, c);
         p.moments = c->moments;
         const unsigned blocks = (unsigned)std::min<long long>((px + 255) / 256, (long long)kNoiseBlocksPerCu * c->n_cu);
         hipLaunchKernelGGL(k_noise, dim3(blocks), dim3(256), 0, c->stream, p, c->mom_frames, ptn::target_q(target),
@@ -3328,9 +2954,9 @@ extern "C" int pt_debug_phase_clock(unsigned long long out[8], int reset) {
 int pt_stats_ex(pt_ctx* c, unsigned long long out[16]) {
     if (!c || !out) return PT_E_ARG;
     std::memcpy(out, c->last_counts, sizeof(c->last_counts));
-    out[13] = c->lds_bytes;
-    out[14] = c->walk_nested ? c->lds_bytes_sk : 0;
-    out[15] = cons_walk_on(c);               // the scene's LDS walk culls (slab_oct_cons)
+    out[13] = c->sf.lds_bytes;
+    out[14] = c->sf.walk_nested ? c->sf.lds_bytes_sk : 0;
+    out[15] = ptl::cons_walk_on(c->sf, c->tun, c->counting);               // the scene's LDS walk culls (slab_oct_cons)
     return PT_OK;
 }
 

@@ -490,3 +490,79 @@ def test_cold_probe_launch_is_invisible(cornell_scene):
         pt.close()
     assert_bitwise(imgs[0], want, "cold render with probe launch")
     assert_bitwise(imgs[1], want, "raster order")
+
+
+# One case per line of csrc/pt_render_kernels.h that no other test of the suite launches (the
+# launch planner, run on the CPU, says which configuration selects which line;
+# tests/test_launch_plan.py checks this table against it): 64x48, 2 frames, bit-exact.
+#   line: COUNT,LDS,MINW,MULTI,SPLIT,PADN,NT,WIDE
+#   scene; variant; rays per pixel; then tuning keys 3 (waves per SIMD), 5 (frames per item:
+#   2 = register mode here), 16 (1 = binary global walk), 17 (wide-walk workgroup); counting
+KERNEL_LINE_CASES = [
+    ("1,1,5,1,0,0,256,0", "cornell", 0, 2, 0, 2, 0, 0, True),
+    ("1,1,5,1,1,0,256,0", "cornell", 0, 2, 0, 0, 0, 0, True),
+    ("1,0,5,0,0,0,256,0", "cornell", 3, 1, 0, 2, 0, 0, True),
+    ("1,0,5,1,0,0,256,0", "cornell", 3, 2, 0, 2, 0, 0, True),
+    ("1,0,5,1,1,0,256,0", "cornell", 3, 2, 0, 0, 0, 0, True),
+    ("0,1,5,0,0,0,256,0", "cornell", 0, 1, 5, 2, 0, 0, False),
+    ("0,1,5,1,0,0,256,0", "cornell", 0, 2, 5, 2, 0, 0, False),
+    ("0,1,6,0,0,0,512,0", "bunny80", 0, 1, 0, 2, 0, 0, False),
+    ("0,1,6,0,0,0,768,0", "bunny150", 0, 1, 0, 2, 0, 0, False),
+    ("0,1,4,0,0,0,1024,0", "bunny380", 0, 1, 0, 2, 0, 0, False),
+    ("0,0,5,0,0,0,256,0", "cornell", 3, 1, 5, 2, 1, 0, False),
+    ("0,0,5,0,1,0,256,0", "cornell", 3, 1, 5, 0, 1, 0, False),
+    ("0,0,5,1,0,0,256,0", "cornell", 3, 2, 5, 2, 1, 0, False),
+    ("0,0,5,1,1,0,256,0", "cornell", 3, 2, 5, 0, 1, 0, False),
+    ("0,0,6,0,0,0,256,0", "cornell", 3, 1, 0, 2, 1, 0, False),
+    ("0,0,6,1,0,0,256,0", "cornell", 3, 2, 0, 2, 1, 0, False),
+    ("0,0,7,0,1,0,256,0", "cornell", 3, 1, 7, 0, 1, 0, False),
+    ("0,0,5,0,0,0,256,1", "cornell", 3, 1, 5, 2, 0, 0, False),
+    ("0,0,7,0,0,0,256,1", "cornell", 3, 1, 7, 2, 0, 0, False),
+    ("0,0,6,0,0,0,512,1", "cornell", 3, 1, 0, 2, 0, 512, False),
+    ("0,0,6,0,1,0,512,1", "cornell", 3, 1, 0, 0, 0, 512, False),
+    ("0,0,6,0,0,0,768,1", "cornell", 3, 1, 0, 2, 0, 768, False),
+    ("0,0,6,0,1,0,768,1", "cornell", 3, 1, 0, 0, 0, 768, False),
+    ("0,0,4,0,0,0,1024,1", "cornell", 3, 1, 0, 2, 0, 1024, False),
+    ("0,0,4,0,1,0,1024,1", "cornell", 3, 1, 0, 0, 0, 1024, False),
+]
+LINE_W, LINE_H, LINE_FRAMES, LINE_BOUNCES = 64, 48, 2, 4
+
+
+def line_scene(name, directory):
+    """Scene of a KERNEL_LINE_CASES row: Cornell, or the mesh stand-in at a triangle count whose
+    LDS copy is shared by 512 / 768 / 1024-thread workgroups."""
+    import pt_scenes
+    if name == "cornell":
+        return H.setupBuffers(*pt_scenes.write_scene("cornell", str(directory)))
+    return H.setupBuffers(*pt_scenes.write_scene("bunny", str(directory), target_tris=int(name[5:])))
+
+
+@pytest.fixture(scope="module")
+def line_reference(tmp_path_factory):
+    """Scene and oracle image per (scene, rays per pixel), computed once."""
+    cache = {}
+
+    def get(name, rpp):
+        if name not in cache:
+            cache[name] = (line_scene(name, tmp_path_factory.mktemp(name)), {})
+        sc, imgs = cache[name]
+        if rpp not in imgs:
+            imgs[rpp] = O.render(sc, LINE_W, LINE_H, max_bounce=LINE_BOUNCES, n_frames=LINE_FRAMES, rpp=rpp)
+        return sc, imgs[rpp]
+    return get
+
+
+@pytest.mark.parametrize("line,scene,variant,rpp,waves,group,wide_off,wide_threads,counting", KERNEL_LINE_CASES,
+                         ids=[c[0] for c in KERNEL_LINE_CASES])
+def test_kernel_list_line(line_reference, line, scene, variant, rpp, waves, group, wide_off, wide_threads, counting):
+    sc, want = line_reference(scene, rpp)
+    pt = H.PathTracer(LINE_W, LINE_H, max_bounce=LINE_BOUNCES, rays_per_pixel=rpp)
+    pt.set_kernel(variant)
+    pt.upload(sc)
+    for key, value in ((3, waves), (5, group), (16, wide_off), (17, wide_threads)):
+        pt.set_key(key, value)
+    pt.set_counting(counting)
+    pt.render(1, LINE_FRAMES, 0)
+    got = pt.read_rgba32f()
+    pt.close()
+    assert_bitwise(got, want, "kernel list line " + line)
