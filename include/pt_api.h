@@ -143,6 +143,10 @@ int pt_stats(pt_ctx* ctx, double* kernel_ms, unsigned long long out[5]);
  * uploaded tree qualifies for the culling walk, it is on (tuning key 15) and the sink image
  * costs no resident workgroup per CU at the set waves per SIMD (key 3), else 0. */
 int pt_stats_ex(pt_ctx* ctx, unsigned long long out[16]);
+/* Render-kernel launches this context has enqueued since pt_create: out[0] on a generic line,
+ * out[1] on the specialised default-path line (tuning key 21).  A captured progressive graph
+ * counts once, at capture; its replays run the line it was captured with. */
+int pt_debug_launches(pt_ctx* ctx, unsigned long long out[2]);
 /* Sum of render-kernel durations (HIP events on the render stream) and the number of
  * launches since the last reset; reset != 0 clears both after reading. */
 int pt_timing(pt_ctx* ctx, double* total_kernel_ms, int* n_launches, int reset);
@@ -197,6 +201,12 @@ int pt_set_kernel(pt_ctx* ctx, int variant);
  * key 20 = work-queue tile shape: 1 = 8x8, 2 = 16x4, 3 = 32x2, 4 = 64x1 pixels (columns x local
  *         rows), 0 = automatic (8x8).  A change drains the context's streams and
  *         drops a captured graph.
+ * key 21 = specialised default-path kernel (0 = automatic, 1 = off: always the generic kernel).
+ *         A frame-split launch of the default configuration -- shaded mode, no flags, one ray
+ *         per pixel, one sphere, a scene staged in LDS with the culling walk, 8x8 tiles in a
+ *         learned order, automatic thresholds and occupancy -- runs a build of the kernel that
+ *         holds these launch-wide facts as constants; every other launch, and
+ *         a context's launches before its first tile-order sort, run the generic one.
  * None of these change the image (each pixel's frames stay in order in one lane). */
 int pt_set_tuning(pt_ctx* ctx, int key, int value);
 

@@ -153,6 +153,21 @@ static KernelKey kernel_key(bool counting, bool lds, bool wide, bool split, int 
     return {false, lds, mw >= 6 ? 6 : 5, multi, split, false, 256, false};
 }
 
+// Whether a launch may run the COMMON instantiation of its key: every fact that kernel holds as a
+// constant is true of this launch.  The key says the rest: not counting, the scene staged in LDS with images padded
+// to kPadNodes, one ray per pixel, frame-split, 7 waves per SIMD, 256 threads.  What the planner cannot see -- the
+// display mode, a learned tile order, a footprint that clips -- enqueue_render checks.
+static bool common_launch(const SceneFacts& f, const Tuning& t, const Image& im, const LaunchPlan& p) {
+    if (t.common_off || !(p.key == kCommonKey)) return false;
+    // no tuning key in the way: automatic occupancy, 8 x 8 tiles, the culling walk.  The thresholds and the walk
+    // floor stay kernel arguments (as constants 52 / 44 / 5 they measured 1.1% slower on C2: the sink walk's yield
+    // test then takes 6 more vector instructions), but a launch that overrides one keeps the generic line, so a
+    // threshold sweep compares one kernel with itself.
+    if (t.minw || t.leaf_thresh || t.shade_thresh || t.trav_floor || im.tile_shift != 0 || !p.cons_walk) return false;
+    if (im.flags != 0) return false;
+    return f.n_spheres == 1 && f.scene_fast != 0 && f.walk_nested && f.root_child >= 0;
+}
+
 LaunchPlan plan_launch(const SceneFacts& f, const Tuning& t, const Image& im, const State& s, int n_frames,
                        bool graph) {
     LaunchPlan p{};
@@ -252,6 +267,7 @@ LaunchPlan plan_launch(const SceneFacts& f, const Tuning& t, const Image& im, co
     // what k_render_sm stages: the scene copy, or the top records / nodes and the shading records
     p.dyn_lds_bytes = p.lds ? lds : (p.wide ? (size_t)p.wide_top * 48 : (size_t)p.n_top * 32) + shade_lds_bytes;
     p.key = kernel_key(s.counting, p.lds, p.wide, p.split, p.mw, im.rpp, p.nt, f.walk_np);
+    p.common = common_launch(f, t, im, p);
     if (p.split) {  // the accumulate pass: the long variant loads 8 frames per group
         p.accum_long = n_frames > kShortLaunch;
         p.accum_moments = s.moments;

@@ -75,10 +75,15 @@ struct Tuning {
     size_t scratch_budget = 0;
     int variant = 0;                // pt_set_kernel: 0, or 3 = the scene stays in global memory
     bool adaptive = true;           // key 2: adaptive tile order
+    int common_off = 0;             // key 21: 1 = never the specialised default-path kernel (LaunchPlan::common)
 };
 
 // the context's share of the image and its device; what else a launch depends on
-struct Image { int width, rows_local, n_tiles, rpp, flags, n_cu; unsigned persist_blocks; };
+struct Image {
+    int width, rows_local, n_tiles, rpp, flags, n_cu;
+    unsigned persist_blocks;
+    int tile_shift = 0;             // work-queue tiles of (8 << tile_shift) x (8 >> tile_shift) pixels (tuning key 20)
+};
 struct State { bool counting, moments, aces_fuse; };
 
 // A k_render_sm instantiation by its template arguments (pt_render_kernels.h lists them).
@@ -96,7 +101,14 @@ struct LaunchPlan {
     bool accum_long, accum_moments, aces_out;   // the accumulate pass of a split launch ...
     unsigned accum_blocks;                      // ... and its grid (256 threads per block)
     KernelKey key;
+    // The launch may run the key's line of PT_RENDER_KERNELS_COMMON (pt_render_kernels.h): the instantiation that
+    // holds the default configuration's launch-uniform facts as constants (common_launch).  Beside the key, not in
+    // it: the launch still has its generic line, which enqueue_render takes when a fact only it can see fails.
+    bool common;
 };
+
+// The template arguments of the one line built with COMMON (the default path of a Cornell-sized scene).
+constexpr KernelKey kCommonKey = {false, true, 7, false, true, true, 256, false};
 
 // Whether the LDS walk culls (also pt_stats_ex[15]), and the bound on a launch's queue ids.
 bool cons_walk_on(const SceneFacts& f, const Tuning& t, bool counting);

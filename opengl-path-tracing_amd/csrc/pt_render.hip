@@ -772,9 +772,36 @@ constexpr int kWaveTraceMax = 16384;
 __device__ unsigned long long g_wave_trace[kWaveTraceMax * 4];
 #endif
 
-template <bool COUNT, bool LDS, int MINW, bool MULTI, bool SPLIT, bool PADN = false, int NT = 256, bool WIDE = false>
+// The launch-uniform facts the state machine branches on.  The generic kernels read them from
+// their arguments, on every trip round the loop; a COMMON instantiation holds the default
+// configuration's as constants (ptl::common_launch and enqueue_render vouch for each), so the
+// untaken sides -- display modes 2-4, Moller-Trumbore, the non-culling walks, the raster tile
+// order, the item division -- are not in its code.  Uniform control flow and address arithmetic
+// only: every lane runs the same operations on the same values either way.  Measured on C2
+// (DESIGN.md §5.2): mode, flags and the culling walk give about 1.8% each, the tile facts 0.3%,
+// the single sphere nothing in time (7 fewer spilled SGPRs); the thresholds and the walk floor
+// are not here because as constants they cost 1.1%.
+template <bool COMMON>
+struct LaunchFacts {
+    const KParams& p;
+    __device__ __forceinline__ int mode() const { return COMMON ? 1 : p.mode; }
+    __device__ __forceinline__ int flags() const { return COMMON ? 0 : p.flags; }
+    __device__ __forceinline__ bool cons_walk() const { return COMMON || p.cons_walk != 0; }
+    __device__ __forceinline__ bool scene_fast() const { return COMMON || p.scene_fast != 0; }
+    __device__ __forceinline__ int n_spheres() const { return COMMON ? 1 : p.sc.n_spheres; }
+    __device__ __forceinline__ int tile_shift() const { return COMMON ? 0 : p.tile_shift; }
+    __device__ __forceinline__ bool tile_perm() const { return COMMON || p.tile_perm != nullptr; }
+    __device__ __forceinline__ bool tile_cost() const { return COMMON || p.tile_cost != nullptr; }
+    // COMMON: the footprint is the image (x_limit >= W; a local row's y is below y_limit)
+    __device__ __forceinline__ bool inside(int cx, int cy) const { return COMMON || ((cx < p.x_limit) & (cy < p.y_limit)); }
+};
+
+template <bool COUNT, bool LDS, int MINW, bool MULTI, bool SPLIT, bool PADN = false, int NT = 256, bool WIDE = false,
+          bool COMMON = false>
 __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
     static_assert(!WIDE || (!LDS && !COUNT), "the wide walk is the global-memory walk of a render build");
+    static_assert(!COMMON || (!COUNT && LDS && !MULTI && SPLIT && PADN), "COMMON is the default path's LDS line");
+    const LaunchFacts<COMMON> F{p};
 #ifdef PT_WAVE_TRACE
     const unsigned long long wt_entry = __builtin_amdgcn_s_memrealtime();
     unsigned wt_items = 0;
@@ -787,10 +814,10 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
         if ((unsigned)(size_t)(__attribute__((address_space(3))) const char*)g_lds != 0u) __builtin_trap();
         // 8 octant images (the culling walk: + its sink image)
         const int N = PADN ? kPadNodes : p.walk_np, T = p.n_slots, nt = 4 * T;
-        const bool sk = !COUNT && p.cons_walk;
+        const bool sk = !COUNT && F.cons_walk();
         const int nn = sk ? 18 * N : 16 * N;
         const float4* wsrc = sk ? p.sc.walk_sk : p.sc.walk_lds;
-        const int nm = 3 * p.n_mats, ns = 2 * p.sc.n_spheres;
+        const int nm = 3 * p.n_mats, ns = 2 * F.n_spheres();
         for (int i = threadIdx.x; i < nn; i += blockDim.x) lds[i] = wsrc[i];   // ready-made image
         for (int i = threadIdx.x; i < nt; i += blockDim.x) lds[nn + (i & 3) * T + (i >> 2)] = p.sc.tris[i];
         for (int i = threadIdx.x; i < nm; i += blockDim.x) lds[nn + nt + i] = p.sc.mats[i];
@@ -853,15 +880,16 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
 #endif
     const f3 cpos = mk(p.cam[0], p.cam[1], p.cam[2]), cfwd = mk(p.cam[3], p.cam[4], p.cam[5]);
     const f3 cright = mk(p.cam[6], p.cam[7], p.cam[8]), cup = mk(p.cam[9], p.cam[10], p.cam[11]);
-    const int tsh = p.tile_shift, tw = 8 << tsh, th = 8 >> tsh;   // tile: tw columns x th local rows
+    const int tsh = F.tile_shift(), tw = 8 << tsh, th = 8 >> tsh;   // tile: tw columns x th local rows
     const int tiles_x = (p.W + tw - 1) >> (3 + tsh);
     const unsigned n_groups = SPLIT ? (unsigned)((p.n_frames + p.group - 1) / p.group) : 1u;
     const unsigned total_ids = (unsigned)tiles_x * (unsigned)((p.rows_local + th - 1) >> (3 - tsh)) * n_groups * 64u;
     const int n_nodes = p.sc.n_nodes;
-    const bool use_tris = !(p.flags & PT_FLAG_NO_TRIANGLES) && n_nodes > 0;
+    const bool use_tris = !(F.flags() & PT_FLAG_NO_TRIANGLES) && n_nodes > 0;
     // walk start for a ray inside the root box: its first child (the counting build walks
     // from the root, so the counts stay the reference's)
-    const int root_skip = (COUNT || p.root_child < 0) ? -1 : p.root_child << (LDS ? 4 : 0);
+    const int root_skip = (COUNT || (!COMMON && p.root_child < 0)) ? -1 : p.root_child << (LDS ? 4 : 0);
+    const bool has_skip = COMMON || root_skip >= 0;
 #ifdef PT_WAVE_TRACE
     const unsigned long long wt_staged = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -936,10 +964,10 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
                         mat = __float_as_int(S.spheres[2 * si + 1].x);
                     }
                     if (pt::dot(normal, d) > 0.0f) normal = normal * -1.0f;
-                    if (p.mode == 2) {
+                    if (F.mode() == 2) {
                         rgb = (normal + mk(1, 1, 1)) * 0.5f;
                         finished = true;
-                    } else if (p.mode == 4) {
+                    } else if (F.mode() == 4) {
                         float s = pt::length(hitp - o);
                         float dist = 1.0f - pt::fsqrt(s + 1.0f) / (s + 1.0f);
                         float q = dist * dist;
@@ -951,7 +979,7 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
                         float kk = 2.0f * pt::dot(normal, d);
                         f3 specular = pt::normalize(d - normal * kk);
                         float4 m0 = S.mats[3 * mat], m1 = S.mats[3 * mat + 1], m2 = S.mats[3 * mat + 2];
-                        if (p.mode == 3) {
+                        if (F.mode() == 3) {
                             rgb = mk(m0.x, m0.y, m0.z);
                             finished = true;
                         } else {
@@ -968,7 +996,7 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
                     }
                 } else {
                     f3 env = mk(0, 0, 0);
-                    if (!(p.flags & PT_FLAG_NO_SKY)) {
+                    if (!(F.flags() & PT_FLAG_NO_SKY)) {
                         f3 dir = pt::normalize(d);
                         float tt = 0.5f * (dir.z + 1.0f);
                         float omt = 1.0f - tt;
@@ -1009,7 +1037,7 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
             }
             if ((st == ST_SHADE) & (bounce < 0) & (lx >= 0) & (k >= (SPLIT ? kend : p.n_frames))) {
                 if (!SPLIT) p.accum[aidx] = acc;
-                if (p.tile_cost && tile_id != ~0u) atomicAdd(&p.tile_cost[tile_id], pcost);
+                if (F.tile_cost() && tile_id != ~0u) atomicAdd(&p.tile_cost[tile_id], pcost);
                 lx = -1;
             }
             // wave-aggregated pull from the work queue.  Frame-split items are short, so
@@ -1047,10 +1075,11 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
                         // item -> (tile, frame group): by the host's exact magic reciprocal
                         // (kernel argument) when it is valid for every item
                         unsigned tile = item;
-                        if (SPLIT) tile = p.grp_magic ? __umulhi(item, p.grp_magic) : item / n_groups;
+                        // (COMMON: the planner's magic is valid, or 0 for items of one group)
+                        if (SPLIT) tile = p.grp_magic ? __umulhi(item, p.grp_magic) : (COMMON ? item : item / n_groups);
                         const int g = SPLIT ? (int)(item - tile * n_groups) : 0;
                         int tx, ty;
-                        if (p.tile_perm) {          // packed (ty << 16) | tx: no division
+                        if (F.tile_perm()) {        // packed (ty << 16) | tx: no division
                             const unsigned pk = p.tile_perm[tile];
                             tx = (int)(pk & 0xffffu);
                             ty = (int)(pk >> 16);
@@ -1062,7 +1091,7 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
                         int cx = tx * tw + (int)(w & (unsigned)(tw - 1));
                         int crow = ty * th + (int)(w >> (3 + tsh));
                         int cy = p.row0 + crow * p.row_stride;
-                        if ((cx < p.W) & (crow < p.rows_local) & (cx < p.x_limit) & (cy < p.y_limit)) {
+                        if ((cx < p.W) & (crow < p.rows_local) & F.inside(cx, cy)) {
                             lx = cx;
 #ifdef PT_WAVE_TRACE
                             wt_items++;
@@ -1087,7 +1116,7 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
                 if (bounce < 0) {    // camera ray due (:514-542)
                     if (r == 0) state = pt::seed(lx, y, p.frame_first + k);
                     float ax = 0.0f, ay = 0.0f;
-                    if (!(p.flags & PT_FLAG_NO_AA)) {
+                    if (!(F.flags() & PT_FLAG_NO_AA)) {
                         ax = pt::random01(state);
                         ay = pt::random01(state);
                     }
@@ -1107,7 +1136,7 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
                 // && of the old form was an exec-mask branch): every origin component 0 or
                 // in [2^-40, 2^60], every direction component in [2^-20, 2] (NaN fails)
                 const bool fast_seg =
-                       (p.scene_fast != 0) & in_guard(o.x, 0x1p-40f, 0x1p60f) & in_guard(o.y, 0x1p-40f, 0x1p60f) &
+                       F.scene_fast() & in_guard(o.x, 0x1p-40f, 0x1p60f) & in_guard(o.y, 0x1p-40f, 0x1p60f) &
                        in_guard(o.z, 0x1p-40f, 0x1p60f) & in_range_abs(d.x, 0x1p-20f, 2.0f) &
                        in_range_abs(d.y, 0x1p-20f, 2.0f) & in_range_abs(d.z, 0x1p-20f, 2.0f);
                 // under the guard |d_i| is in [2^-20, 2]: rcp_fast is the exact RN(1/d_i); rd = 0
@@ -1117,8 +1146,8 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
                 if (COUNT && ray_has_nan(o, d)) c.nan++;
                 t = __builtin_huge_valf();
                 hprim = -1;
-                if (!(p.flags & PT_FLAG_NO_SPHERES)) {
-                    for (int si = 0; si < p.sc.n_spheres; si++) {
+                if (!(F.flags() & PT_FLAG_NO_SPHERES)) {
+                    for (int si = 0; si < F.n_spheres(); si++) {
                         float4 s0 = S.spheres[2 * si];
                         f3 oc = o - mk(s0.x, s0.y, s0.z);
                         float a = pt::dot(d, d);
@@ -1138,7 +1167,7 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
                 const bool walk = use_tris & (COUNT || !ray_has_nan(o, d));
                 // inside the root box (all three axes, inclusive) each axis has near <= 0 <=
                 // far, so the exact slab says hit for any t >= 0: skip the root's test
-                const bool inside = (root_skip >= 0) & fast_seg & (o.x >= p.root_box[0]) & (o.x <= p.root_box[1]) &
+                const bool inside = has_skip & fast_seg & (o.x >= p.root_box[0]) & (o.x <= p.root_box[1]) &
                                     (o.y >= p.root_box[2]) & (o.y <= p.root_box[3]) & (o.z >= p.root_box[4]) &
                                     (o.z <= p.root_box[5]);
                 const int img = (LDS && fast_seg) ? oct_base(d, S.np << 5) : 0;   // octant image
@@ -1166,7 +1195,7 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
                     s0 = gc & ~1;                            // slots 2g, 2g+1
                     cop = (gc & 1) != 0;
                 }
-                if (LDS && !COUNT && p.cons_walk) {   // sinks carry the pair k only
+                if (LDS && !COUNT && F.cons_walk()) {   // sinks carry the pair k only
                     s0 = 2 * leaf;
                     cop = __float_as_int(tri_quad<LDS>(S, s0 + 1, 1).w) != 0;
                 }
@@ -1176,7 +1205,7 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
             }
             float h1 = -1.0f, h2 = -1.0f;
             bool ca = false, cb = false;   // the chosen triangle certifies its leaf's box (pt_wide.h)
-            if (p.flags & PT_FLAG_MOLLER_TRUMBORE) {   // wave-uniform
+            if (F.flags() & PT_FLAG_MOLLER_TRUMBORE) {   // wave-uniform
                 if (at) {
                     h1 = tri_mt(tri_quad<LDS>(S, s0, 1), tri_quad<LDS>(S, s0, 2), tri_quad<LDS>(S, s0, 3), o, d);
                     h2 = tri_mt(tri_quad<LDS>(S, s0 + 1, 1), tri_quad<LDS>(S, s0 + 1, 2),
@@ -1190,7 +1219,7 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
                 c1 = win_open(h1, t) & ((h1 < h2) | (h2 < 0.0001f));
                 c2 = !c1 & win_open(h2, t);
             }
-            if (LDS && !COUNT && p.cons_walk) {
+            if (LDS && !COUNT && F.cons_walk()) {
                 // the culling walk stopped here on the conservative test: the reference tests
                 // this leaf's triangles only if its box passes the exact test at this t, and
                 // only a triangle that moves t makes the difference (a leaf's hit and miss
@@ -1236,7 +1265,7 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
             // the per-node IEEE-division branch.
             const unsigned long long live = LDS ? mS | mL | mT : __ballot(st != ST_DONE);
             const bool all_fast = LDS ? (__ballot(fast) & mT) == mT : __all(fast || st != ST_TRAV);
-            if (LDS && !COUNT && p.cons_walk) {    // the culling walk (kernel argument: uniform)
+            if (LDS && !COUNT && F.cons_walk()) {    // the culling walk (kernel argument: uniform)
                 if (all_fast)
                     trav_walk<true, COUNT, LDS, PADN, true>(S, o, d, rd, fast, t, live, mT, mL, mS, p.leaf_thresh, p.shade_thresh, p.trav_floor, st, bi, leaf, c);
                 else
@@ -1586,6 +1615,7 @@ struct pt_ctx {
     float cam[12] = {0};
     float last_ms = 0.0f;
     unsigned long long last_counts[16] = {0};
+    unsigned long long n_line_launches[2] = {0, 0};   // render launches enqueued on a generic / a COMMON line (pt_debug_launches)
     bool count_pending = false;
     // asynchronous presentation (pt_present_begin / _end): per buffer a pinned host image and
     // its copy event; the device view is rgba8 (one, as the copies and the passes that write
@@ -2166,6 +2196,7 @@ static const TuningKey kTuningKeys[] = {
     {18, &ptl::Tuning::overlap_bpc, [](int v) { return v >= 0 && v <= 8; },
      "overlapped render blocks per CU must be 1..8 (0 = automatic)", false},
     {19, &ptl::Tuning::cert_off, in_0_1, "leaf re-test certificate: 0 = automatic, 1 = off", true},
+    {21, &ptl::Tuning::common_off, in_0_1, "specialised default-path kernel: 0 = automatic, 1 = off", true},
 };
 
 int pt_set_tuning(pt_ctx* c, int key, int value) {
@@ -2250,7 +2281,8 @@ constexpr int kProbeFrames = 2, kProbeMin = 64;  // cold long renders: a sorted 
 
 // The launch planner's view of the context (pt_launch_plan.h).
 static ptl::Image plan_image(const pt_ctx* c) {
-    return {c->cfg.width, c->rows_local, c->n_tiles, c->cfg.rays_per_pixel, c->cfg.flags, c->n_cu, c->persist_blocks};
+    return {c->cfg.width, c->rows_local, c->n_tiles, c->cfg.rays_per_pixel, c->cfg.flags, c->n_cu, c->persist_blocks,
+            c->tile_shift};
 }
 static ptl::State plan_state(const pt_ctx* c) { return {c->counting, c->moments != nullptr, c->aces_fuse}; }
 static ptl::LaunchPlan plan(const pt_ctx* c, int n_frames, bool graph) {
@@ -2309,10 +2341,27 @@ struct RenderKernel { ptl::KernelKey key; void (*fn)(KParams); };
 #define PT_X(C, L, MW, M, S, P, NT, W) {{C, L, MW, M, S, P, NT, W}, k_render_sm<C, L, MW, M, S, P, NT, W>},
 static const RenderKernel kRenderKernels[] = {PT_RENDER_KERNELS(PT_X)};
 #undef PT_X
-static const RenderKernel* find_kernel(const ptl::KernelKey& key) {
+// ... and the lines also built with COMMON (the launch-uniform facts as constants), by the same key
+#define PT_X(C, L, MW, M, S, P, NT, W) {{C, L, MW, M, S, P, NT, W}, k_render_sm<C, L, MW, M, S, P, NT, W, true>},
+static const RenderKernel kRenderKernelsCommon[] = {PT_RENDER_KERNELS_COMMON(PT_X)};
+#undef PT_X
+static const RenderKernel* find_kernel(const ptl::KernelKey& key, bool common = false) {
+    if (common) {
+        for (const RenderKernel& k : kRenderKernelsCommon)
+            if (k.key == key) return &k;
+        return nullptr;
+    }
     for (const RenderKernel& k : kRenderKernels)
         if (k.key == key) return &k;
     return nullptr;
+}
+// The facts of a COMMON line the planner cannot see (ptl::common_launch has the rest): the shaded display mode, a
+// tile order and the cost counts that keep it current (a context's first launches have no learned order yet and run
+// the generic line), a footprint that does not clip, an item division the kernel has by magic or not at all.
+static bool common_params_ok(const pt_ctx* c, const KParams& p, int n_frames) {
+    const int n_groups = (n_frames + p.group - 1) / p.group;
+    return (p.mode < 2 || p.mode > 4) && p.tile_perm && p.tile_cost && c->order_sorted && p.tile_shift == 0 &&
+           p.x_limit >= p.W && p.y_limit >= p.H && (p.grp_magic != 0 || n_groups == 1);
 }
 typedef void (*KParamsKernel)(KParams);
 static KParamsKernel accum_kernel(const ptl::LaunchPlan& pl) {   // the accumulate pass of a split launch
@@ -2398,7 +2447,8 @@ static int enqueue_render(pt_ctx* c, int frame_first, int n_frames, int acc_firs
         p.rgb = c->d_rgb;
     }
     if (c->rows_local == 0) return PT_OK;
-    const RenderKernel* kernel = find_kernel(pl.key);
+    const bool common = pl.common && common_params_ok(c, p, n_frames);
+    const RenderKernel* kernel = find_kernel(pl.key, common);
     if (!kernel) {
         const ptl::KernelKey& k = pl.key;
         char key[96];
@@ -2414,6 +2464,7 @@ static int enqueue_render(pt_ctx* c, int frame_first, int n_frames, int acc_firs
     if (pl.overlap) p.reset_work = work;
     else HIPCHK(c, hipMemsetAsync(work, 0, kQueueSet * sizeof(unsigned), rs));
     hipLaunchKernelGGL(kernel->fn, dim3(pl.blocks), dim3((unsigned)kernel->key.nt), pl.dyn_lds_bytes, rs, p);
+    c->n_line_launches[common]++;
     if (pl.split) {
         if (pl.overlap) {
             HIPCHK(c, hipEventRecord(c->ev_rdone[re], rs));
@@ -2957,6 +3008,13 @@ int pt_stats_ex(pt_ctx* c, unsigned long long out[16]) {
     out[13] = c->sf.lds_bytes;
     out[14] = c->sf.walk_nested ? c->sf.lds_bytes_sk : 0;
     out[15] = ptl::cons_walk_on(c->sf, c->tun, c->counting);               // the scene's LDS walk culls (slab_oct_cons)
+    return PT_OK;
+}
+
+int pt_debug_launches(pt_ctx* c, unsigned long long out[2]) {
+    if (!c || !out) return PT_E_ARG;
+    out[0] = c->n_line_launches[0];
+    out[1] = c->n_line_launches[1];
     return PT_OK;
 }
 

@@ -60,4 +60,9 @@
     X(false, false, 6, false, true,  false, 768, true)                                         \
     X(false, false, 4, false, false, false, 1024, true)                                        \
     X(false, false, 4, false, true,  false, 1024, true)
+// The lines also built with the template's last argument, COMMON: the default configuration's launch-uniform facts as
+// constants (pt_render.hip, LaunchFacts).  A launch runs one when its plan says `common` and enqueue_render finds the
+// remaining facts true; its generic line above stays the fall-back.
+#define PT_RENDER_KERNELS_COMMON(X)                                                            \
+    X(false, true,  7, false, true,  true,  256, false)
 // clang-format on

@@ -125,6 +125,7 @@ def lib():
             "pt_copy_rows_device": (ip, [vp, vp, C.c_size_t]),
             "pt_timing": (ip, [vp, C.POINTER(C.c_double), C.POINTER(ip), ip]),
             "pt_stats_ex": (ip, [vp, np.ctypeslib.ndpointer(np.uint64)]),
+            "pt_debug_launches": (ip, [vp, np.ctypeslib.ndpointer(np.uint64)]),
             "pt_set_tuning": (ip, [vp, ip, ip]),
             "pt_progressive_setup": (ip, [vp, ip, ip]),
             "pt_progressive_reset": (ip, [vp, ip]),
@@ -377,6 +378,17 @@ class PathTracer:
         """Tuning key 15: the LDS walk's conservative culling (on by default where the tree
         qualifies).  Never changes the image."""
         self._check(lib().pt_set_tuning(self.h, 15, 0 if enable else 1))
+
+    def set_common(self, enable):
+        """Tuning key 21: the specialised default-path kernel (on by default where the launch
+        qualifies).  Never changes the image."""
+        self._check(lib().pt_set_tuning(self.h, 21, 0 if enable else 1))
+
+    def launches(self):
+        """pt_debug_launches -> (launches on a generic line, on the specialised line)."""
+        v = np.zeros(2, np.uint64)
+        self._check(lib().pt_debug_launches(self.h, v))
+        return int(v[0]), int(v[1])
 
     def set_key(self, key, value):
         """Raw pt_set_tuning(key, value) (experiments)."""
