@@ -147,6 +147,12 @@ int pt_stats_ex(pt_ctx* ctx, unsigned long long out[16]);
  * out[1] on the specialised default-path line (tuning key 21).  A captured progressive graph
  * counts once, at capture; its replays run the line it was captured with. */
 int pt_debug_launches(pt_ctx* ctx, unsigned long long out[2]);
+/* The window clause of the LDS culling walk (tuning key 22): *active = 1 when the context's
+ * LDS launches run it (the walk culls, the key leaves it on, no Moller-Trumbore, every
+ * triangle of the scene inside the clause's conditions), *slack = the uploaded scene's window
+ * slack (the largest of its three axes; 0 for a scene outside the conditions).  Either
+ * pointer may be null. */
+int pt_debug_window_cull(pt_ctx* ctx, int* active, float* slack);
 /* Sum of render-kernel durations (HIP events on the render stream) and the number of
  * launches since the last reset; reset != 0 clears both after reading. */
 int pt_timing(pt_ctx* ctx, double* total_kernel_ms, int* n_launches, int reset);
@@ -207,6 +213,9 @@ int pt_set_kernel(pt_ctx* ctx, int variant);
  *         learned order, automatic thresholds and occupancy -- runs a build of the kernel that
  *         holds these launch-wide facts as constants; every other launch, and
  *         a context's launches before its first tile-order sort, run the generic one.
+ * key 22 = window clause of the LDS culling walk (0 = automatic, 1 = off).  The walk skips a
+ *         box that ends before the distance window (1e-4, t) in which a triangle can be
+ *         accepted; off, launches run the generic kernel without the clause.
  * None of these change the image (each pixel's frames stay in order in one lane). */
 int pt_set_tuning(pt_ctx* ctx, int key, int value);
 

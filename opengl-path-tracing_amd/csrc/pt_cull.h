@@ -1,0 +1,190 @@
+// pt_cull.h -- the node test of the LDS culling walk, shared by the HIP kernel
+// (pt_render.hip), pt_upload_scene (the scene's window slack) and the CPU walk model
+// (tests/cull/window_cull_sim.cpp).
+//
+// The test is conservative on two sides.  Inside the exact-reciprocal guard every quotient is
+// finite and normal or zero.  With u = 2^-24, q = RN(RN(b - o) / d) the reference's quotient and
+// rd = RN(1/d), the margins are folded into per-ray addends:
+//   near = fma(b, rd, ol),  far = fma(b, rd, oh),  ord = RN(-o * rd),
+//   ol = ord - E_i,  oh = ord + E_i + W_i |rd_i|,
+//   E_i = 2^-19 M_i |rd_i| + 2^-17 |ord_i|   (M_i: the scene's largest |coordinate| on axis i),
+//   W_i = 20u max_j |o_j| + ws_i             (ws: the scene's window slack, window_slack below).
+//
+// (1) The t side, as before.  |b - o| <= M_i + |o_i| and |q| <= M_i |rd_i| + 1.01 |ord_i|; the
+// error of every fma quotient against q, 4.2u |q| + 2.1u |ord| + 2.1u (oh - ord) including the
+// roundings of the addends, is below E_i / 3 + 2.1u W_i |rd_i|, so near <= q_near and far >=
+// q_far on every axis: a node the reference's test accepts (tn <= tf and tn <= t) is accepted
+// here.
+//
+// (2) The window side.  The reference only ever accepts a triangle distance h with h > 0.0001f
+// (computeShader.c:411, :420), so a leaf whose box ends before that distance cannot move t, nor
+// can any box nested inside it: the walk also requires far >= c_lo on every axis, with
+// c_lo = 1e-4 (1 - 2^-10), as max(tn, c_lo) <= min(tf, t) -- t > 1e-4 > c_lo always (t starts at
+// +inf and only takes accepted distances), so c_lo may share the max with tn and one compare
+// remains.  One more VALU per node (v_max_f32 with a constant operand), no register across the
+// walk: the per-ray safety margin sits in oh.
+//
+// Lemma.  Let a ray inside the guard and a leaf triangle T = (v0, v1, v2) of a scene that passed
+// pt_upload_scene with the clause on be such that the reference accepts T: hit_triangle
+// (:274-307) returns h with h > 0.0001f and all three edge tests true.  Then far_i >= c_lo on
+// every axis for T's leaf box and every ancestor's.
+//
+// Proof.  All data are binary32 values read as reals, |.| of a vector is its 2-norm.  n =
+// normalize(cross(v1 - v0, v2 - v0)) and d0 = -dot(n, v0) are T's stored plane as pt_upload_scene
+// rounds them, N = (v1 - v0) x (v2 - v0) exactly, D = n . N, L the longest edge, X_i - m_i the
+// extent of T's vertices on axis i, rho = max_k |n . v_k + d0|, M2 = |(M_x, M_y, M_z)|,
+// kappa = L^2 / D.  window_slack admits T only if D > 0, kappa <= 2^14 and rho <= L (in float64;
+// its own rounding, 2^-50 relative, disappears in the factor 1.25 below).
+//   (a) Edge tests.  The hit point is p_i = RN(o_i + RN(d_i h)).  Edge test k evaluates
+//   e_k = dot(n, cross(E_k, w)), E_k = v_{k+1} - v_k, w = p - v_k: each of its six terms
+//   n_a E_b w_c passes through at most seven roundings (E, w, E w, the cross's subtraction, the
+//   product with n, two sums), and sum_a |n_a| (|E_b| |w_c| + |E_c| |w_b|) <= sqrt(2) |n| |E| |w|
+//   (Cauchy-Schwarz twice), |n| <= 1 + 4u: e_k > 0 gives e^_k > -eps_k for the exact e^_k =
+//   n . (E_k x (p - v_k)), eps_k = 10.1u |E_k| |p - v_k| + 2^-140 (the last term: underflows).
+//   Write p = sum_j l_j v_j + s n with sum_j l_j = 1 (possible as D != 0).  e^_k is linear in p,
+//   vanishes on edge k's line and along n, and equals D at the opposite vertex: e^_k =
+//   D l_{k+2}.  So every l_j > -eta, eta = max_k eps_k / D; at most two of them are negative, so
+//   q = sum_j l_j v_j exceeds the interval [m_i, X_i] by at most 2 eta (X_i - m_i).
+//   |q - v_k| <= (1 + 5 eta) L and |p - v_k| <= |q - v_k| + sigma with sigma = |s n|, so
+//   eta L <= 10.1u kappa ((1 + 5 eta) L + sigma) + 2^-140 L / D, and with 50.5u kappa < 0.05:
+//   eta L <= a (L + sigma) + z,  a = 10.7u kappa <= 0.0105,  z = 1.06 * 2^-140 L / D.
+//   (b) The plane.  n . p + d0 = sum_j l_j (n . v_j + d0) + s |n|^2, so sigma <= 1.001 (|g| +
+//   rho (1 + 6 eta)) with g = (n . p + d0) / |n|.  h = RN(-nu / Delta) with nu = RN(RN(n . o) +
+//   d0) = (n . o + d0) + e_nu, Delta = RN(n . d) = n . d + e_Delta, |e_nu| <= 4.01u (|n| |o| +
+//   |d0|), |e_Delta| <= 3.01u |n| |d|.  Then n . o + d0 + h (n . d) = -e_nu - nu theta -
+//   h e_Delta with |theta| <= u, |nu| <= 1.02 h |n| |d|, and the two roundings of p add at most
+//   1.01u |n| (h |d| + |p|).  With h |d| <= 1.01 (|p| + |o|), |o| <= sqrt(3) omax (omax =
+//   max_j |o_j|) and |p| <= M2 + sqrt(3) delta, where delta bounds p's excess over T's vertex
+//   intervals:  |g| <= u (16 omax + 6.2 M2 + 4.06 |d0| + 10.8 delta).
+//   (c) Together.  rho eta <= (rho / L) (a (L + sigma) + z) <= a rho + a sigma + z, delta <=
+//   2 eta L + sigma and L <= 2 M2; solving the linear inequalities of (a) and (b) with a <=
+//   0.0105 gives
+//     sigma <= 17.1u omax + sigma_T,   sigma_T = u (7.2 M2 + 4.4 |d0|) + 1.14 rho + 6.5 z,
+//     p_i in [m_i - delta_i, X_i + delta_i],
+//     delta_i = 2 eta (X_i - m_i) + sigma <= 17.5u omax + [21.4u kappa (X_i - m_i) + 1.021 sigma_T + 2 z].
+//   The bracket is delta_T,i; ws_i = 1.25 max_T delta_T,i.
+//   (d) The far quotient.  For d_i > 0 the leaf box's far plane is b = max_i >= X_i (every leaf
+//   box contains its triangles' vertices: checked at upload), so b - o_i >= p_i - o_i - delta_i >=
+//   d_i h (1 - u) - 1.01u |p_i| - delta_i and Q = (b - o_i) / d_i >= h (1 - u) - (1.02u (M_i +
+//   delta_i) + delta_i) |rd_i| (1 + u); d_i < 0 mirrors it with b = min_i.  far = RN(b rd + oh) >=
+//   Q + (oh - ord) - (u |Q| + 1.01u |ord| + u |oh| + u |far|) >= Q + 0.9 E_i + 0.99 W_i |rd_i| (the
+//   bracket is below E_i / 14 + 2.1u (oh - ord), as in (1)).  0.9 E_i >= 28u M_i |rd_i| covers
+//   1.03u M_i |rd_i|, and 0.99 W_i >= 0.99 (20u omax + 1.25 delta_T,i) (1 - 2u) covers
+//   1.001 delta_i: far >= h (1 - u) >= 0.0001f > c_lo, with a relative margin of 2^-10.
+//   (e) Ancestors.  On a nested tree (pt_bvh_culling_ok) an ancestor's far plane lies at or beyond
+//   the leaf's on every axis, so b' rd >= b rd as reals, and RN of the fma is monotone.  QED.
+//
+//   Overflow.  The rounding model above needs finite values.  h > 1e-4 and |d_i| >= 2^-20 keep
+//   d_i h above the subnormals; if d_i h overflows, p_i and every w_i are infinite, and an edge
+//   test can only be +inf if for each axis a with n_a != 0 the products n_a E^k_b sign(w_c) are
+//   positive for all three edges k -- impossible, since the edge vectors sum to zero (and a zero
+//   E^k_b makes the term NaN): no such hit is accepted.
+// A triangle whose normal is not finite (zero area) never passes hit_triangle and asks nothing.
+// A scene with a triangle outside (a)'s conditions runs without the clause (c_lo = -inf, ws = 0:
+// the walk of (1) alone).
+// Moller-Trumbore (PT_FLAG_MOLLER_TRUMBORE) accepts through another test with another window
+// (t > 1e-7): that mode runs with c_lo = -inf, as does tuning key 22 = 1 (the A/B switch).
+#pragma once
+
+#include "pt_math.h"
+
+namespace ptc {
+
+// c_lo: just below the reference's acceptance threshold 0.0001f (1e-4 (1 - 2^-10), rounded)
+constexpr float kWindowLo = 0.0001f * 0x1.ff8p-1f;
+// the per-ray part of W: 20u max_j |o_j| (the lemma needs 1.02 * 17.5u)
+constexpr float kWindowRay = 0x1.4p-20f;
+
+PT_HD float min_t(float tf, float t) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    // min(tf, t) for non-NaN operands as one v_med3: fminf would add a canonicalising v_max on
+    // the loop-carried t (both are finite or +inf inside the guard)
+    return __builtin_amdgcn_fmed3f(tf, t, -__builtin_huge_valf());
+#else
+    return fminf(tf, t);
+#endif
+}
+
+// The per-ray addends ol = ord - E, oh = ord + E + W |rd| (cm[i] = 2^-19 M_i rounded up, ws the
+// scene's window slack per axis).
+PT_HD void cull_addends(pt::f3 o, pt::f3 rd, const float cm[3], const float ws[3], pt::f3& ol, pt::f3& oh) {
+    const pt::f3 ord = pt::mk(-(o.x * rd.x), -(o.y * rd.y), -(o.z * rd.z));
+    const float ax = __builtin_fabsf(rd.x), ay = __builtin_fabsf(rd.y), az = __builtin_fabsf(rd.z);
+    const pt::f3 e = pt::mk(__builtin_fmaf(cm[0], ax, 0x1p-17f * __builtin_fabsf(ord.x)),
+                            __builtin_fmaf(cm[1], ay, 0x1p-17f * __builtin_fabsf(ord.y)),
+                            __builtin_fmaf(cm[2], az, 0x1p-17f * __builtin_fabsf(ord.z)));
+    const float omax = fmaxf(fmaxf(__builtin_fabsf(o.x), __builtin_fabsf(o.y)), __builtin_fabsf(o.z));
+    const float wx = __builtin_fmaf(kWindowRay, omax, ws[0]), wy = __builtin_fmaf(kWindowRay, omax, ws[1]),
+                wz = __builtin_fmaf(kWindowRay, omax, ws[2]);
+    ol = ord - e;
+    oh = ord + pt::mk(__builtin_fmaf(wx, ax, e.x), __builtin_fmaf(wy, ay, e.y), __builtin_fmaf(wz, az, e.z));
+}
+
+// The node test on an octant image (bounds near-first for the ray's direction signs):
+// (nx, fx, ny, fy) = the node's lo quad, (nz, fz) = its hi quad's .xy.  c_lo = kWindowLo, or -inf
+// for the test without the window clause.
+PT_HD bool cull_hit(float nx, float fx, float ny, float fy, float nz, float fz, pt::f3 rd, pt::f3 ol, pt::f3 oh,
+                    float cur_t, float c_lo) {
+    const float xn = __builtin_fmaf(nx, rd.x, ol.x), xf = __builtin_fmaf(fx, rd.x, oh.x);
+    const float yn = __builtin_fmaf(ny, rd.y, ol.y), yf = __builtin_fmaf(fy, rd.y, oh.y);
+    const float zn = __builtin_fmaf(nz, rd.z, ol.z), zf = __builtin_fmaf(fz, rd.z, oh.z);
+    const float tn = fmaxf(fmaxf(xn, yn), zn);
+    const float tf = fminf(fminf(xf, yf), zf);
+    return fmaxf(tn, c_lo) <= min_t(tf, cur_t);   // one compare
+}
+
+// Host only.  The scene's window slack ws_i = 1.25 max_T delta_T,i over the triangles of its leaves
+// (the lemma's (c)), rounded up; false (and ws = 0) when a triangle falls outside the lemma's
+// conditions or the slack is not finite: the scene's walk then runs without the clause.  bvh: the reference's node records (12 floats: min, -, max, -, t0, t1, hit, miss),
+// tris: 16 floats per triangle.
+inline bool window_slack(const float* bvh, int n_nodes, const float* tris, float ws[3]) {
+    const double u = 0x1p-24;
+    const float inf = __builtin_huge_valf();
+    ws[0] = ws[1] = ws[2] = 0.0f;
+    if (n_nodes <= 0) return true;
+    double M2 = 0.0;
+    for (int q = 0; q < 3; q++) {
+        const double m = fmax(fabs((double)bvh[q]), fabs((double)bvh[4 + q]));
+        M2 += m * m;
+    }
+    M2 = sqrt(M2);
+    double worst[3] = {0.0, 0.0, 0.0};
+    for (int i = 0; i < n_nodes; i++) {
+        const float* nd = bvh + 12 * (size_t)i;
+        if (!(nd[8] > -1.0f)) continue;
+        for (int k = 0; k < 2; k++) {
+            const float* t = tris + 16 * (size_t)(int)nd[8 + k];
+            const pt::f3 v0 = pt::mk(t[0], t[1], t[2]), v1 = pt::mk(t[4], t[5], t[6]), v2 = pt::mk(t[8], t[9], t[10]);
+            const pt::f3 n = pt::normalize(pt::cross(v1 - v0, v2 - v0));   // as put_tri
+            const float d0 = -pt::dot(n, v0);
+            if (!(fabs((double)n.x) + fabs((double)n.y) + fabs((double)n.z) < (double)inf)) continue;   // never hit
+            const double V[3][3] = {{v0.x, v0.y, v0.z}, {v1.x, v1.y, v1.z}, {v2.x, v2.y, v2.z}};
+            const double nn[3] = {n.x, n.y, n.z};
+            double E1[3], E2[3], L2 = 0.0, rho = 0.0;
+            for (int q = 0; q < 3; q++) { E1[q] = V[1][q] - V[0][q]; E2[q] = V[2][q] - V[0][q]; }
+            const double N[3] = {E1[1] * E2[2] - E2[1] * E1[2], E1[2] * E2[0] - E2[2] * E1[0], E1[0] * E2[1] - E2[0] * E1[1]};
+            const double D = nn[0] * N[0] + nn[1] * N[1] + nn[2] * N[2];
+            for (int a = 0; a < 3; a++) {
+                const int b = (a + 1) % 3;
+                double l2 = 0.0;
+                for (int q = 0; q < 3; q++) l2 += (V[b][q] - V[a][q]) * (V[b][q] - V[a][q]);
+                L2 = fmax(L2, l2);
+                rho = fmax(rho, fabs(nn[0] * V[a][0] + nn[1] * V[a][1] + nn[2] * V[a][2] + (double)d0));
+            }
+            const double L = sqrt(L2);
+            if (!(D > 0.0) || !(L2 <= 0x1p14 * D) || !(rho <= L)) return false;
+            const double kappa = L2 / D, z = 1.06 * 0x1p-140 * L / D;
+            const double sigma_t = u * (7.2 * M2 + 4.4 * fabs((double)d0)) + 1.14 * rho + 6.5 * z;
+            for (int q = 0; q < 3; q++) {
+                const double ext = fmax(fmax(V[0][q], V[1][q]), V[2][q]) - fmin(fmin(V[0][q], V[1][q]), V[2][q]);
+                worst[q] = fmax(worst[q], 21.4 * u * kappa * ext + 1.021 * sigma_t + 2.0 * z);
+            }
+        }
+    }
+    for (int q = 0; q < 3; q++)
+        if (!(worst[q] < 0x1p60)) return false;
+    for (int q = 0; q < 3; q++) ws[q] = nextafterf((float)(1.25 * worst[q] * (1.0 + 0x1p-20)), inf);
+    return true;
+}
+
+}  // namespace ptc

@@ -35,6 +35,13 @@ bool cons_walk_on(const SceneFacts& f, const Tuning& t, bool counting) {
     return blocks(f.lds_bytes_sk) >= blocks(f.lds_bytes);
 }
 
+// Whether the culling walk runs with the window clause (pt_cull.h; also pt_debug_window_cull): the walk culls, key 22
+// leaves the clause on, the scene is inside the conditions of the clause's lemma, and triangles are accepted by
+// hit_triangle, whose window the lemma is about.
+bool window_cull_on(const SceneFacts& f, const Tuning& t, int flags, bool counting) {
+    return cons_walk_on(f, t, counting) && !t.win_off && !f.win_bad && !(flags & PT_FLAG_MOLLER_TRUMBORE);
+}
+
 // Whether a global-memory launch walks the wide tree: the scene has one (a nested tree), it lies
 // inside the scene half of the exact-reciprocal guard (otherwise no lane could use it), tuning key 16 leaves it on,
 // nothing is counted (counting builds keep the binary walk: their counts are the reference's), and the occupancy is
@@ -158,7 +165,7 @@ static KernelKey kernel_key(bool counting, bool lds, bool wide, bool split, int 
 // to kPadNodes, one ray per pixel, frame-split, 7 waves per SIMD, 256 threads.  What the planner cannot see -- the
 // display mode, a learned tile order, a footprint that clips -- enqueue_render checks.
 static bool common_launch(const SceneFacts& f, const Tuning& t, const Image& im, const LaunchPlan& p) {
-    if (t.common_off || !(p.key == kCommonKey)) return false;
+    if (t.common_off || t.win_off || f.win_bad || !(p.key == kCommonKey)) return false;   // (the window clause's c_lo is a constant there)
     // no tuning key in the way: automatic occupancy, 8 x 8 tiles, the culling walk.  The thresholds and the walk
     // floor stay kernel arguments (as constants 52 / 44 / 5 they measured 1.1% slower on C2: the sink walk's yield
     // test then takes 6 more vector instructions), but a launch that overrides one keeps the generic line, so a

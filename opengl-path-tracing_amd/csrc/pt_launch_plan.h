@@ -52,6 +52,8 @@ struct SceneFacts {
     float root_box[6] = {0, 0, 0, 0, 0, 0};
     int root_child = -1;
     float cons_m[3] = {0, 0, 0};    // KParams::cons_m
+    float win_slack[3] = {0, 0, 0}; // KParams::win_slack (ptc::window_slack)
+    bool win_bad = false;           // the scene is outside the window clause's conditions (pt_cull.h): no clause
     float wide_cw[3] = {0, 0, 0};
 };
 
@@ -76,6 +78,7 @@ struct Tuning {
     int variant = 0;                // pt_set_kernel: 0, or 3 = the scene stays in global memory
     bool adaptive = true;           // key 2: adaptive tile order
     int common_off = 0;             // key 21: 1 = never the specialised default-path kernel (LaunchPlan::common)
+    int win_off = 0;                // key 22: 1 = the culling walk without its window clause (pt_cull.h)
 };
 
 // the context's share of the image and its device; what else a launch depends on
@@ -112,6 +115,7 @@ constexpr KernelKey kCommonKey = {false, true, 7, false, true, true, 256, false}
 
 // Whether the LDS walk culls (also pt_stats_ex[15]), and the bound on a launch's queue ids.
 bool cons_walk_on(const SceneFacts& f, const Tuning& t, bool counting);
+bool window_cull_on(const SceneFacts& f, const Tuning& t, int flags, bool counting);
 unsigned long long id_limit(const Tuning& t, const Image& im);
 
 // Everything a launch of n_frames decides before it touches HIP.  `graph`: the launch is captured

@@ -20,6 +20,7 @@
 //   leaf code  : k << 2 | coplanar << 1 | single (k = leaf pair index, slots 2k and 2k+1)
 //   mat   48 B : {color.rgb, smoothness}, {emission*strength, specProb}, {specular.rgb, 0}
 //   sphere 32 B: {c.xyz, r*r}, {matIdx, 0, 0, 0}
+#include "pt_cull.h"
 #include "pt_launch_plan.h"
 #include "pt_math.h"
 #include "pt_noise.h"
@@ -102,6 +103,8 @@ struct KParams {
     int shade_lds;                 // global-memory scene: materials + spheres staged in LDS too
     int cons_walk;                 // LDS scene: the culling walk (slab_oct_cons, exact leaf re-test)
     float cons_m[3];               // ... 2^-19 * the scene's largest |coordinate| per axis, rounded up
+    float win_slack[3];            // ... the scene's window slack per axis (ptc::window_slack)
+    float win_lo;                  // ... c_lo of the window clause: ptc::kWindowLo, or -inf (off, Moller-Trumbore)
     int wide_top;                  // wide walk (WIDE instantiations): records [0, wide_top) staged in LDS
     float wide_cw[3];              // ... 2^-18 * the scene's largest |coordinate| per axis, rounded up (WRay)
     int leaf_cert;                 // culling / wide walk: skip the exact leaf re-test where the hit certifies it
@@ -255,6 +258,7 @@ struct SceneView {
     const float4* spheres;
     int np, tp;    // plane strides (float4) of the state-machine kernel's LDS copy
     float cm[3];   // culling walk: 2^-19 * the scene's largest |coordinate| per axis (slab_oct_cons)
+    float ws[3], clo;   // ... the scene's window slack and the window clause's c_lo (pt_cull.h)
     const float4* wrec;    // wide walk: records (global), their first `wtop` staged in LDS planes
     const float4* wlbox;   // ... exact leaf boxes
     int wtop;
@@ -359,28 +363,15 @@ __device__ __forceinline__ bool slab_oct(float4 A, float4 B, f3 o, f3 d, f3 rd, 
     return tn <= __builtin_amdgcn_fmed3f(tf, cur_t, -__builtin_huge_valf());   // as slab_oct_cons
 }
 
-// Conservative slab_oct of the culling walk.  Inside the exact-reciprocal
-// guard every quotient is finite and normal or zero.  With u = 2^-24, q = RN(RN(b - o) / d)
-// the exact quotient and rd = RN(1/d), the margin is folded into per-axis addends:
-// near = fma(b, rd, ord - E_i), far = fma(b, rd, ord + E_i) with ord = RN(-o * rd) and
-// E_i = 2^-19 M_i |rd_i| + 2^-17 |ord_i| (M_i: the largest |coordinate| of the scene on axis i,
-// so |b - o| <= M_i + |o_i| and |q| <= M_i |rd_i| + 1.01 |ord_i|): the error of every fma
-// quotient, 4.2u |q| + 2.1u |ord| + 2.1u E_i including the rounding of ord -+ E_i, is below
-// E_i, so near <= q_near and far >= q_far on every axis, and an exact hit (tn <= tf and
-// tn <= t) is always a hit here.  Only culling may use it: a node it accepts and the exact
+// Conservative slab_oct of the culling walk (pt_cull.h has the test, its margins and the lemma of
+// the window clause).  Only culling may use it: a node it accepts and the exact
 // test rejects is walked in vain, and a leaf reached that way is rejected by the exact test
 // of its own box, which the leaf phase runs before a triangle moves t.  (Measured forms:
 // RN(b - o) * rd with a relative margin per node +2.2%, fma with a per-node margin +4.7%,
 // this one +7.1% on C2 over the exact test.)
-// ol / oh: the per-ray addends ord - E_i, ord + E_i
-__device__ __forceinline__ bool slab_oct_cons(float4 A, float4 B, f3 rd, f3 ol, f3 oh, float cur_t) {
-    float xn = __builtin_fmaf(A.x, rd.x, ol.x), xf = __builtin_fmaf(A.y, rd.x, oh.x);
-    float yn = __builtin_fmaf(A.z, rd.y, ol.y), yf = __builtin_fmaf(A.w, rd.y, oh.y);
-    float zn = __builtin_fmaf(B.x, rd.z, ol.z), zf = __builtin_fmaf(B.y, rd.z, oh.z);
-    float tn = fmaxf(fmaxf(xn, yn), zn);
-    float tf = fminf(fminf(xf, yf), zf);
-    // one compare; fminf would add a canonicalizing v_max on the loop-carried t
-    return tn <= __builtin_amdgcn_fmed3f(tf, cur_t, -__builtin_huge_valf());
+// ol / oh: the per-ray addends (ptc::cull_addends); c_lo: the window clause's constant
+__device__ __forceinline__ bool slab_oct_cons(float4 A, float4 B, f3 rd, f3 ol, f3 oh, float cur_t, float c_lo) {
+    return ptc::cull_hit(A.x, A.y, A.z, A.w, B.x, B.y, rd, ol, oh, cur_t, c_lo);
 }
 
 // Byte offset of the ray's octant image in the LDS walk: image k = sx | sy << 1 | sz << 2
@@ -568,14 +559,7 @@ __device__ __forceinline__ void trav_walk(const SceneView& S, f3 o, f3 d, f3 rd,
                                           bool eligible = true) {
     const int min_thresh = leaf_thresh < shade_thresh ? leaf_thresh : shade_thresh;
     f3 ol = mk(0, 0, 0), oh = mk(0, 0, 0);
-    if (CONS) {   // S.cm[i] = 2^-19 M_i (slab_oct_cons)
-        const f3 ord = mk(-(o.x * rd.x), -(o.y * rd.y), -(o.z * rd.z));
-        const f3 e = mk(__builtin_fmaf(S.cm[0], __builtin_fabsf(rd.x), 0x1p-17f * __builtin_fabsf(ord.x)),
-                        __builtin_fmaf(S.cm[1], __builtin_fabsf(rd.y), 0x1p-17f * __builtin_fabsf(ord.y)),
-                        __builtin_fmaf(S.cm[2], __builtin_fabsf(rd.z), 0x1p-17f * __builtin_fabsf(ord.z)));
-        ol = ord - e;
-        oh = ord + e;
-    }
+    if (CONS) ptc::cull_addends(o, rd, S.cm, S.ws, ol, oh);   // S.cm[i] = 2^-19 M_i
     // Inside the walk one register carries the lane's state (WalkLinks): w >= 0 the next
     // node, w == -1 the chain ended (-> SHADE), w <= -2 stopped at the hit leaf with code
     // -2 - w (-> LEAF, bi = w).  st / bi are written back once at the end.
@@ -604,7 +588,7 @@ __device__ __forceinline__ void trav_walk(const SceneView& S, f3 o, f3 d, f3 rd,
             float4 lo, hi;
             node_at<LDS, PADN>(S, w, lo, hi);
             const int a = __float_as_int(hi.z), b = __float_as_int(hi.w);
-            const bool hb = (ALL_FAST || fast) ? slab_oct_cons(lo, hi, rd, ol, oh, t) : slab(lo, hi, o, d, t);
+            const bool hb = (ALL_FAST || fast) ? slab_oct_cons(lo, hi, rd, ol, oh, t, S.clo) : slab(lo, hi, o, d, t);
 #ifdef PT_PHASE_CLOCK
             if (w < sink0) diag_tick(c.tw, c.tl);
 #endif
@@ -645,7 +629,7 @@ __device__ __forceinline__ void trav_walk(const SceneView& S, f3 o, f3 d, f3 rd,
             float4 lo, hi;
             node_at<LDS, PADN>(S, w, lo, hi);
             int a = __float_as_int(hi.z), b = __float_as_int(hi.w);
-            bool hb = (ALL_FAST || fast) ? (LDS ? (CONS ? slab_oct_cons(lo, hi, rd, ol, oh, t)
+            bool hb = (ALL_FAST || fast) ? (LDS ? (CONS ? slab_oct_cons(lo, hi, rd, ol, oh, t, S.clo)
                                                         : slab_oct(lo, hi, o, d, rd, t))
                                                  : slab_fast(lo, hi, o, d, rd, t))
                                          : slab(lo, hi, o, d, t);
@@ -788,6 +772,7 @@ struct LaunchFacts {
     __device__ __forceinline__ int flags() const { return COMMON ? 0 : p.flags; }
     __device__ __forceinline__ bool cons_walk() const { return COMMON || p.cons_walk != 0; }
     __device__ __forceinline__ bool scene_fast() const { return COMMON || p.scene_fast != 0; }
+    __device__ __forceinline__ float win_lo() const { return COMMON ? ptc::kWindowLo : p.win_lo; }
     __device__ __forceinline__ int n_spheres() const { return COMMON ? 1 : p.sc.n_spheres; }
     __device__ __forceinline__ int tile_shift() const { return COMMON ? 0 : p.tile_shift; }
     __device__ __forceinline__ bool tile_perm() const { return COMMON || p.tile_perm != nullptr; }
@@ -839,6 +824,10 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
         S.cm[0] = p.cons_m[0];
         S.cm[1] = p.cons_m[1];
         S.cm[2] = p.cons_m[2];
+        S.ws[0] = p.win_slack[0];
+        S.ws[1] = p.win_slack[1];
+        S.ws[2] = p.win_slack[2];
+        S.clo = F.win_lo();
     } else {
         S.nodes = p.sc.nodes;     // reference layout; the walk image is for LDS only
         S.tris = p.sc.tris;
@@ -2102,6 +2091,10 @@ int pt_upload_scene(pt_ctx* c, const float* tris, int n_tris, const float* bvh, 
                     if (!(nd[q] <= t[4 * v + q] && t[4 * v + q] <= nd[4 + q])) c->sf.leaf_cert_ok = false;
         }
     }
+    // the window clause of the culling walk (pt_cull.h): its lemma needs the leaf boxes to contain
+    // their triangles and every triangle inside the conditions window_slack checks
+    c->sf.win_slack[0] = c->sf.win_slack[1] = c->sf.win_slack[2] = 0.0f;
+    c->sf.win_bad = !(nested && c->sf.leaf_cert_ok && ptc::window_slack(bvh, n_nodes, tris, c->sf.win_slack));
     c->order_sorted = false;      // the next sort pools the new scene's first short launches
     c->order_skip = 0;
     if (n_nodes > 0) {   // every box lies in the root box (nested): M_i bounds each |coordinate|
@@ -2197,6 +2190,7 @@ static const TuningKey kTuningKeys[] = {
      "overlapped render blocks per CU must be 1..8 (0 = automatic)", false},
     {19, &ptl::Tuning::cert_off, in_0_1, "leaf re-test certificate: 0 = automatic, 1 = off", true},
     {21, &ptl::Tuning::common_off, in_0_1, "specialised default-path kernel: 0 = automatic, 1 = off", true},
+    {22, &ptl::Tuning::win_off, in_0_1, "window clause of the culling walk: 0 = automatic, 1 = off", true},
 };
 
 int pt_set_tuning(pt_ctx* c, int key, int value) {
@@ -2400,6 +2394,8 @@ static KParams fill_params(const pt_ctx* c, const ptl::LaunchPlan& pl, int frame
     // scene facts
     p.n_slots = c->sf.n_slots, p.walk_np = c->sf.walk_np, p.n_mats = c->sf.n_mats, p.scene_fast = c->sf.scene_fast;
     std::memcpy(p.cons_m, c->sf.cons_m, sizeof(p.cons_m));
+    std::memcpy(p.win_slack, c->sf.win_slack, sizeof(p.win_slack));
+    p.win_lo = ptl::window_cull_on(c->sf, c->tun, c->cfg.flags, c->counting) ? ptc::kWindowLo : -__builtin_huge_valf();
     std::memcpy(p.root_box, c->sf.root_box, sizeof(p.root_box));
     p.root_child = c->sf.root_child;
     // the plan
@@ -3008,6 +3004,13 @@ int pt_stats_ex(pt_ctx* c, unsigned long long out[16]) {
     out[13] = c->sf.lds_bytes;
     out[14] = c->sf.walk_nested ? c->sf.lds_bytes_sk : 0;
     out[15] = ptl::cons_walk_on(c->sf, c->tun, c->counting);               // the scene's LDS walk culls (slab_oct_cons)
+    return PT_OK;
+}
+
+int pt_debug_window_cull(pt_ctx* c, int* active, float* slack) {
+    if (!c) return PT_E_ARG;
+    if (active) *active = ptl::window_cull_on(c->sf, c->tun, c->cfg.flags, c->counting) ? 1 : 0;
+    if (slack) *slack = std::max(c->sf.win_slack[0], std::max(c->sf.win_slack[1], c->sf.win_slack[2]));
     return PT_OK;
 }
 

@@ -126,6 +126,7 @@ def lib():
             "pt_timing": (ip, [vp, C.POINTER(C.c_double), C.POINTER(ip), ip]),
             "pt_stats_ex": (ip, [vp, np.ctypeslib.ndpointer(np.uint64)]),
             "pt_debug_launches": (ip, [vp, np.ctypeslib.ndpointer(np.uint64)]),
+            "pt_debug_window_cull": (ip, [vp, C.POINTER(ip), C.POINTER(fp)]),
             "pt_set_tuning": (ip, [vp, ip, ip]),
             "pt_progressive_setup": (ip, [vp, ip, ip]),
             "pt_progressive_reset": (ip, [vp, ip]),
@@ -383,6 +384,17 @@ class PathTracer:
         """Tuning key 21: the specialised default-path kernel (on by default where the launch
         qualifies).  Never changes the image."""
         self._check(lib().pt_set_tuning(self.h, 21, 0 if enable else 1))
+
+    def set_window_cull(self, enable):
+        """Tuning key 22: the window clause of the LDS culling walk (on by default; DESIGN.md
+        §5.6).  Never changes the image."""
+        self._check(lib().pt_set_tuning(self.h, 22, 0 if enable else 1))
+
+    def window_cull(self):
+        """pt_debug_window_cull -> (the clause is active, the scene's window slack)."""
+        a, s = C.c_int(), C.c_float()
+        self._check(lib().pt_debug_window_cull(self.h, C.byref(a), C.byref(s)))
+        return bool(a.value), float(s.value)
 
     def launches(self):
         """pt_debug_launches -> (launches on a generic line, on the specialised line)."""

@@ -1,0 +1,374 @@
+// TEST INFRASTRUCTURE: CPU model of the LDS culling walk with its window clause (pt_cull.h,
+// DESIGN.md §5.6) against the reference's binary32 walk (calculateRayCollision,
+// computeShader.c:367-432; bvh_intersect :309-365; hit_triangle :274-307).  It runs the SAME
+// node test, per-ray addends and window slack the kernel and pt_upload_scene use
+// (ptc::cull_hit / cull_addends / window_slack, compiled for the host) and fails on
+//   (a) a segment whose final t (bitwise) or triangle differs from the reference's,
+//   (b) a leaf at which the reference accepts a triangle while the culling test (with the
+//       clause) rejects that leaf or one of its ancestors at the t of that moment,
+//   (c) a node the reference's exact test accepts and the test without the clause rejects.
+// It reports how many of the reference's leaf visits the clause alone removes.
+//
+// usage: window_cull_sim scene.bin [stride] [bounces] [adversarial_rays]
+//   scene.bin: int32 n_tris, n_nodes, n_spheres, then float32 tris (16 per), nodes (12 per),
+//   spheres (8 per), camera (12: pos, dir, 0...) -- written by tests/test_window_cull.py.
+// Exit status 0 = no violation, 3 = the tree does not qualify for the culling walk.
+// Output: one JSON line of statistics.
+#include "../../opengl-path-tracing_amd/csrc/pt_cull.h"
+
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <utility>
+#include <vector>
+
+using pt::f3;
+using pt::mk;
+
+namespace {
+
+std::vector<float> tris, nodes, sph;
+std::vector<int> parent;
+int nt = 0, nn = 0, ns = 0;
+float cam[12], cm[3], ws[3] = {0, 0, 0};
+
+// computeShader.c:309-365 in IEEE division (the reference's exact test)
+bool slab_exact(const float* lo, const float* hi, f3 o, f3 d, float cur_t) {
+    float tmin = (lo[0] - o.x) / d.x, tmax = (hi[0] - o.x) / d.x;
+    if (tmin > tmax) std::swap(tmin, tmax);
+    float tymin = (lo[1] - o.y) / d.y, tymax = (hi[1] - o.y) / d.y;
+    if (tymin > tymax) std::swap(tymin, tymax);
+    if ((tmin > tymax) || (tymin > tmax)) return false;
+    if (tymin > tmin) tmin = tymin;
+    if (tymax < tmax) tmax = tymax;
+    float tzmin = (lo[2] - o.z) / d.z, tzmax = (hi[2] - o.z) / d.z;
+    if (tzmin > tzmax) std::swap(tzmin, tzmax);
+    if ((tmin > tzmax) || (tzmin > tmax)) return false;
+    if (tzmin > tmin) tmin = tzmin;
+    return !(tmin > cur_t);
+}
+bool node_exact(int i, f3 o, f3 d, float t) {
+    const float* b = &nodes[12 * (size_t)i];
+    return slab_exact(b, b + 4, o, d, t);
+}
+
+f3 ld3(const float* p) { return mk(p[0], p[1], p[2]); }
+
+// :274-307
+float hit_triangle(f3 o, f3 d, int ti) {
+    const float* tr = &tris[16 * (size_t)ti];
+    const f3 v0 = ld3(tr), v1 = ld3(tr + 4), v2 = ld3(tr + 8);
+    const f3 n = pt::normalize(pt::cross(v1 - v0, v2 - v0));
+    const float dd = -pt::dot(n, v0);
+    const float t = -(pt::dot(n, o) + dd) / pt::dot(n, d);
+    if (t < 0.0f) return -1.0f;
+    const f3 p = o + d * t;
+    if (pt::dot(n, pt::cross(v1 - v0, p - v0)) > 0.0f && pt::dot(n, pt::cross(v2 - v1, p - v1)) > 0.0f &&
+        pt::dot(n, pt::cross(v0 - v2, p - v2)) > 0.0f)
+        return t;
+    return -1.0f;
+}
+
+float sphere_t(f3 o, f3 d) {   // :372-385
+    float t = INFINITY;
+    for (int si = 0; si < ns; si++) {
+        const float* s = &sph[8 * (size_t)si];
+        const f3 oc = o - ld3(s);
+        const float a = pt::dot(d, d), hb = pt::dot(oc, d), c = pt::dot(oc, oc) - s[3] * s[3];
+        const float disc = hb * hb - a * c;
+        const float ht = disc < 0.0f ? -1.0f : (-hb - std::sqrt(disc)) / a;
+        if (ht > 0.0001f && ht < t) t = ht;
+    }
+    return t;
+}
+
+// the leaf's 2-way choice (:411-428) at t; returns whether t moves
+bool leaf_choice(int bnode, f3 o, f3 d, float t, float& nt_, int& ntri) {
+    const float* b = &nodes[12 * (size_t)bnode];
+    const int t0 = (int)b[8], t1 = (int)b[9];
+    const float h1 = hit_triangle(o, d, t0), h2 = hit_triangle(o, d, t1);
+    if (h1 > 0.0001f && h1 < t && (h1 < h2 || h2 < 0.0001f)) { nt_ = h1; ntri = t0; return true; }
+    if (h2 > 0.0001f && h2 < t) { nt_ = h2; ntri = t1; return true; }
+    return false;
+}
+
+// the kernel's test of node i: its bounds near-first for the ray's direction signs (the octant
+// images of the LDS walk)
+struct CRay { f3 rd, ol, oh; bool sx, sy, sz; };
+CRay make_ray(f3 o, f3 d) {
+    CRay r;
+    r.rd = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+    ptc::cull_addends(o, r.rd, cm, ws, r.ol, r.oh);
+    r.sx = std::signbit(d.x); r.sy = std::signbit(d.y); r.sz = std::signbit(d.z);
+    return r;
+}
+bool node_cull(int i, const CRay& r, float t, float c_lo) {
+    const float* b = &nodes[12 * (size_t)i];
+    return ptc::cull_hit(r.sx ? b[4] : b[0], r.sx ? b[0] : b[4], r.sy ? b[5] : b[1], r.sy ? b[1] : b[5],
+                         r.sz ? b[6] : b[2], r.sz ? b[2] : b[6], r.rd, r.ol, r.oh, t, c_lo);
+}
+bool chain_cull(int i, const CRay& r, float t, float c_lo) {   // node i and every ancestor
+    for (; i >= 0; i = parent[i])
+        if (!node_cull(i, r, t, c_lo)) return false;
+    return true;
+}
+
+bool in_guard(f3 o, f3 d) {   // the exact-reciprocal guard, ray half
+    auto g0 = [](float v) { float a = std::fabs(v); return v == 0.0f || (a >= 0x1p-40f && a <= 0x1p60f); };
+    auto g1 = [](float v) { float a = std::fabs(v); return a >= 0x1p-20f && a <= 2.0f; };
+    return g0(o.x) && g0(o.y) && g0(o.z) && g1(d.x) && g1(d.y) && g1(d.z);
+}
+
+const float kNoWindow = -INFINITY;
+float c_lo_on = ptc::kWindowLo;
+long window_violations = 0, cons_violations = 0, mismatches = 0, slow = 0, near_hits = 0;
+struct Acc { double segs = 0, ref_nodes = 0, ref_leaves = 0, removed = 0, off_nodes = 0, off_leaves = 0, on_nodes = 0, on_leaves = 0; };
+
+struct Out { float t; int tri; long nodes, leaves; };
+// The reference walk; for guarded rays it also checks (b) / (c) at every node it visits and
+// counts the leaf visits the clause alone removes.
+Out ref_walk(f3 o, f3 d, float t0, bool guarded, const CRay& cr, Acc& A) {
+    Out r{t0, -1, 0, 0};
+    for (int bi = 0; bi > -1;) {
+        const float* b = &nodes[12 * (size_t)bi];
+        const bool hb = node_exact(bi, o, d, r.t);
+        r.nodes++;
+        if (guarded && hb && !node_cull(bi, cr, r.t, kNoWindow)) cons_violations++;
+        const int next = hb ? (int)b[10] : (int)b[11];
+        if (hb && b[8] > -1.0f) {
+            r.leaves++;
+            const bool kept = !guarded || chain_cull(bi, cr, r.t, c_lo_on);
+            if (guarded && !kept && chain_cull(bi, cr, r.t, kNoWindow)) A.removed++;
+            float t2;
+            int tri;
+            if (leaf_choice(bi, o, d, r.t, t2, tri)) {
+                if (!kept) {
+                    if (window_violations < 10)
+                        std::fprintf(stderr, "WINDOW o=(%a,%a,%a) d=(%a,%a,%a): leaf %d accepts t=%a, culled\n", o.x, o.y,
+                                     o.z, d.x, d.y, d.z, bi, t2);
+                    window_violations++;
+                }
+                if (t2 < 4e-4f) near_hits++;
+                r.t = t2;
+                r.tri = tri;
+            }
+        }
+        bi = next;
+    }
+    return r;
+}
+
+// The culling walk of the kernel: the conservative test at every node, and at a leaf the
+// reference's 2-way choice, whose winner moves t only if the leaf's own box passes the exact
+// test (the leaf phase's re-test).
+Out cull_walk(f3 o, f3 d, float t0, const CRay& cr, float c_lo) {
+    Out r{t0, -1, 0, 0};
+    for (int bi = 0; bi > -1;) {
+        const float* b = &nodes[12 * (size_t)bi];
+        const bool hb = node_cull(bi, cr, r.t, c_lo);
+        r.nodes++;
+        const int next = hb ? (int)b[10] : (int)b[11];
+        if (hb && b[8] > -1.0f) {
+            r.leaves++;
+            float t2;
+            int tri;
+            if (leaf_choice(bi, o, d, r.t, t2, tri) && node_exact(bi, o, d, r.t)) { r.t = t2; r.tri = tri; }
+        }
+        bi = next;
+    }
+    return r;
+}
+
+void segment(f3 o, f3 d, Acc& A, float* t_out, int* tri_out) {
+    const float t0 = sphere_t(o, d);
+    const bool guarded = in_guard(o, d);
+    CRay cr{};
+    if (guarded) cr = make_ray(o, d);
+    const Out ro = ref_walk(o, d, t0, guarded, cr, A);
+    *t_out = ro.t;
+    *tri_out = ro.tri;
+    if (!guarded) { slow++; return; }
+    A.segs++;
+    A.ref_nodes += ro.nodes;
+    A.ref_leaves += ro.leaves;
+    const Out off = cull_walk(o, d, t0, cr, kNoWindow), on = cull_walk(o, d, t0, cr, c_lo_on);
+    A.off_nodes += off.nodes; A.off_leaves += off.leaves;
+    A.on_nodes += on.nodes; A.on_leaves += on.leaves;
+    for (const Out* w : {&off, &on}) {
+        uint32_t a, b;
+        std::memcpy(&a, &ro.t, 4);
+        std::memcpy(&b, &w->t, 4);
+        if (a != b || ro.tri != w->tri) {
+            if (mismatches < 10)
+                std::fprintf(stderr, "MISMATCH o=(%a,%a,%a) d=(%a,%a,%a): ref t=%a tri=%d, cull(%s) t=%a tri=%d\n", o.x, o.y,
+                             o.z, d.x, d.y, d.z, ro.t, ro.tri, w == &on ? "on" : "off", w->t, w->tri);
+            mismatches++;
+        }
+    }
+}
+
+float ulps(float v, int k) {   // v moved k units in the last place (k < 0: toward -inf)
+    for (int i = 0; i < std::abs(k); i++) v = std::nextafterf(v, k > 0 ? INFINITY : -INFINITY);
+    return v;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    if (argc < 2) { std::fprintf(stderr, "usage: window_cull_sim scene.bin [stride] [bounces] [adversarial]\n"); return 2; }
+    FILE* f = std::fopen(argv[1], "rb");
+    if (!f) return 2;
+    int hdr[3];
+    if (std::fread(hdr, 4, 3, f) != 3) return 2;
+    nt = hdr[0]; nn = hdr[1]; ns = hdr[2];
+    if (nt < 1 || nn < 1) return 2;
+    tris.resize(16 * (size_t)nt); nodes.resize(12 * (size_t)nn); sph.resize(8 * (size_t)ns);
+    if (std::fread(tris.data(), 4, tris.size(), f) != tris.size() || std::fread(nodes.data(), 4, nodes.size(), f) != nodes.size() ||
+        std::fread(sph.data(), 4, sph.size(), f) != sph.size() || std::fread(cam, 4, 12, f) != 12)
+        return 2;
+    std::fclose(f);
+    const int stride = argc > 2 ? std::atoi(argv[2]) : 16;
+    const int bounces = argc > 3 ? std::atoi(argv[3]) : 8;
+    const long adversarial = argc > 4 ? std::atol(argv[4]) : 0;
+    // the conditions of pt_upload_scene: a full binary tree threaded in preorder whose boxes nest
+    // (parents from the links: an internal node's children are its hit link and that child's miss
+    // link), and leaf boxes that contain their triangles' vertices
+    parent.assign(nn, -1);
+    bool nested = true, leaf_ok = true;
+    for (int i = 0; i < nn && nested; i++) {
+        const float* b = &nodes[12 * (size_t)i];
+        if (b[8] > -1.0f) {
+            for (int k = 0; k < 2; k++) {
+                const int ti = (int)b[8 + k];
+                if (ti < 0 || ti >= nt) { nested = false; break; }
+                for (int v = 0; v < 3; v++)
+                    for (int q = 0; q < 3; q++)
+                        if (!(b[q] <= tris[16 * (size_t)ti + 4 * v + q] && tris[16 * (size_t)ti + 4 * v + q] <= b[4 + q])) leaf_ok = false;
+            }
+            continue;
+        }
+        const int l = (int)b[10];
+        if (l <= i || l >= nn) { nested = false; break; }
+        const int r = (int)nodes[12 * (size_t)l + 11];
+        if (r <= l || r >= nn) { nested = false; break; }
+        for (int c : {l, r}) {
+            parent[c] = i;
+            const float* cb = &nodes[12 * (size_t)c];
+            for (int q = 0; q < 3; q++)
+                if (!(b[q] <= cb[q] && cb[4 + q] <= b[4 + q])) nested = false;
+        }
+    }
+    for (int i = 1; i < nn; i++)
+        if (parent[i] < 0) nested = false;
+    if (!nested) {
+        std::printf("{\"nested\": false}\n");
+        return 3;
+    }
+    for (int q = 0; q < 3; q++) {   // KParams::cons_m as pt_upload_scene rounds it
+        const double m = std::fmax(std::fabs((double)nodes[q]), std::fabs((double)nodes[4 + q]));
+        cm[q] = (float)std::ldexp(m * (1.0 + 0x1p-20), -19);
+    }
+    const bool win_ok = leaf_ok && ptc::window_slack(nodes.data(), nn, tris.data(), ws);
+    if (!win_ok) ws[0] = ws[1] = ws[2] = 0.0f;
+    c_lo_on = win_ok ? ptc::kWindowLo : kNoWindow;   // a scene outside the lemma's conditions runs without the clause
+
+    // diffuse paths: camera basis (computeShader.c:517-522), 1920x1080 grid sampled every `stride` pixels
+    const int Wd = 1920, Hd = 1080;
+    const f3 pos = mk(cam[0], cam[1], cam[2]);
+    const f3 fwd = pt::normalize(mk(cam[4], cam[5], cam[6]));
+    const f3 right = pt::normalize(pt::cross(fwd, mk(0, 0, 1)));
+    const f3 up = (pt::normalize(pt::cross(right, fwd)) * (float)Hd) / (float)Wd;
+    Acc P;
+    if (stride > 0)
+        for (int y = 0; y < Hd; y += stride)
+            for (int x = 0; x < Wd; x += stride) {
+                uint32_t st = pt::seed(x, y, 1);
+                const float u = ((float)x + pt::random01(st)) / (float)Wd - 0.5f;
+                const float v = ((float)y + pt::random01(st)) / (float)Hd - 0.5f;
+                f3 o = pos, d = pt::normalize((fwd + right * u) + up * v);
+                for (int bnc = 0; bnc <= bounces; bnc++) {
+                    float t;
+                    int tri;
+                    segment(o, d, P, &t, &tri);
+                    if (tri < 0) break;   // (a sphere hit ends the path here: the model follows triangles)
+                    const float* tr = &tris[16 * (size_t)tri];
+                    const f3 v0 = ld3(tr), v1 = ld3(tr + 4), v2 = ld3(tr + 8);
+                    f3 n = pt::normalize(pt::cross(v1 - v0, v2 - v0));
+                    if (pt::dot(n, d) > 0.0f) n = n * -1.0f;
+                    o = o + d * t;
+                    d = pt::normalize(n + pt::random_unit_vector(st));
+                }
+            }
+    // adversarial rays.  Origins: on a triangle's plane (a point of the triangle, or of its
+    // plane beside it), on a face / edge / corner of a node box, each also moved 1..4 ulps
+    // either way on every axis.  Directions: toward a point of another triangle or box, random,
+    // and grazing the origin's triangle with |n . d| = 2^-k, k = 0..20, on either side.
+    Acc Q;
+    uint32_t st = 2463534242u;
+    auto rnd = [&]() { return pt::random01(st); };
+    auto tri_point = [&](int ti, bool inside) {
+        const float* tr = &tris[16 * (size_t)ti];
+        const f3 v0 = ld3(tr), v1 = ld3(tr + 4), v2 = ld3(tr + 8);
+        float a = rnd(), b = rnd();
+        if (inside && a + b > 1.0f) { a = 1.0f - a; b = 1.0f - b; }
+        if (!inside) { a = 2.0f * a - 0.5f; b = 2.0f * b - 0.5f; }
+        const uint32_t r = pt::next_random(st) % 8u;
+        if (r == 0) { a = 0.0f; }            // on an edge
+        if (r == 1) { a = 0.0f; b = 0.0f; }  // a vertex
+        return (v0 + (v1 - v0) * a) + (v2 - v0) * b;
+    };
+    auto box_point = [&](int ni) {
+        const float* nd = &nodes[12 * (size_t)ni];
+        float p[3];
+        for (int q = 0; q < 3; q++) {
+            const uint32_t r = pt::next_random(st) % 4u;
+            p[q] = r == 0 ? nd[q] : r == 1 ? nd[4 + q] : nd[q] + (nd[4 + q] - nd[q]) * rnd();
+        }
+        return mk(p[0], p[1], p[2]);
+    };
+    for (long k = 0; k < adversarial; k++) {
+        const int ta = (int)(pt::next_random(st) % (uint32_t)nt), tb = (int)(pt::next_random(st) % (uint32_t)nt);
+        const uint32_t ok = pt::next_random(st) % 4u;
+        f3 o = ok == 3 ? box_point((int)(pt::next_random(st) % (uint32_t)nn)) : tri_point(ta, ok != 2);
+        if (pt::next_random(st) % 2u) {
+            const int m = 1 + (int)(pt::next_random(st) % 4u);
+            o.x = ulps(o.x, (pt::next_random(st) % 3u) == 0 ? 0 : ((pt::next_random(st) & 1u) ? m : -m));
+            o.y = ulps(o.y, (pt::next_random(st) % 3u) == 0 ? 0 : ((pt::next_random(st) & 1u) ? m : -m));
+            o.z = ulps(o.z, (pt::next_random(st) % 3u) == 0 ? 0 : ((pt::next_random(st) & 1u) ? m : -m));
+        }
+        f3 d;
+        const uint32_t dk = pt::next_random(st) % 4u;
+        if (dk == 0) {
+            d = tri_point(tb, true) - o;
+        } else if (dk == 1) {
+            d = box_point((int)(pt::next_random(st) % (uint32_t)nn)) - o;
+        } else if (dk == 2) {
+            d = pt::random_unit_vector(st);
+        } else {   // grazing triangle ta's plane
+            const float* tr = &tris[16 * (size_t)ta];
+            const f3 v0 = ld3(tr), v1 = ld3(tr + 4), v2 = ld3(tr + 8);
+            const f3 n = pt::normalize(pt::cross(v1 - v0, v2 - v0));
+            f3 tg = pt::normalize((v1 - v0) * (rnd() - 0.5f) + (v2 - v0) * (rnd() - 0.5f));
+            const float s = std::ldexp((pt::next_random(st) & 1u) ? 1.0f : -1.0f, -(int)(pt::next_random(st) % 21u));
+            d = tg + n * s;
+        }
+        if (!(pt::dot(d, d) > 0.0f)) continue;
+        d = pt::normalize(d);
+        float t;
+        int tri;
+        segment(o, d, Q, &t, &tri);
+    }
+    const auto frac = [](const Acc& a) { return a.ref_leaves > 0 ? a.removed / a.ref_leaves : 0.0; };
+    const auto per = [](double v, const Acc& a) { return a.segs > 0 ? v / a.segs : 0.0; };
+    std::printf("{\"nested\": true, \"window_on\": %s, \"n_tris\": %d, \"n_nodes\": %d, \"window_slack\": %.9g, \"path_segments\": %.0f, "
+                "\"adv_segments\": %.0f, \"slow\": %ld, \"mismatches\": %ld, \"window_violations\": %ld, "
+                "\"cons_violations\": %ld, \"near_hits\": %ld, "
+                "\"path_ref_leaves\": %.4f, \"path_removed\": %.0f, \"path_removed_frac\": %.4f, \"path_ref_nodes\": %.4f, "
+                "\"path_off_nodes\": %.4f, \"path_off_leaves\": %.4f, \"path_on_nodes\": %.4f, \"path_on_leaves\": %.4f, "
+                "\"adv_ref_leaves\": %.4f, \"adv_removed\": %.0f, \"adv_removed_frac\": %.4f, \"adv_on_leaves\": %.4f}\n",
+                win_ok ? "true" : "false", nt, nn, (double)std::fmax(ws[0], std::fmax(ws[1], ws[2])), P.segs, Q.segs, slow, mismatches, window_violations, cons_violations, near_hits,
+                per(P.ref_leaves, P), P.removed, frac(P), per(P.ref_nodes, P), per(P.off_nodes, P), per(P.off_leaves, P),
+                per(P.on_nodes, P), per(P.on_leaves, P), per(Q.ref_leaves, Q), Q.removed, frac(Q), per(Q.on_leaves, Q));
+    return (mismatches || window_violations || cons_violations) ? 1 : 0;
+}
