@@ -1,5 +1,5 @@
 // pt_cull.h -- the node test of the LDS culling walk, shared by the HIP kernel
-// (pt_render.hip), pt_upload_scene (the scene's window slack) and the CPU walk model
+// (pt_render.hip), the scene packer (pt_scene_pack.h: the scene's window slack) and the CPU walk model
 // (tests/cull/window_cull_sim.cpp).
 //
 // The test is conservative on two sides.  Inside the exact-reciprocal guard every quotient is

@@ -16,6 +16,7 @@
 #include "../../include/pt_api.h"
 #include "../../include/pt_group.h"
 #include "pt_group_plan.h"
+#include "pt_scene_pack.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -26,8 +27,8 @@
 #include <vector>
 
 // internal hooks of pt_render.hip (not part of the public ABI): kSceneBufs device scene
-// buffers of a context, and the flag that lets a replicated context render
-constexpr int kSceneBufs = 10;
+// buffers of a context (ptp::SceneBuf), and the flag that lets a replicated context render
+constexpr int kSceneBufs = ptp::kBufs;
 extern "C" int pt__scene_replicate_layout(pt_ctx* dst, const pt_ctx* src, void* dptr[kSceneBufs],
                                           const void* sptr[kSceneBufs], size_t bytes[kSceneBufs]);
 extern "C" int pt__scene_set_ready(pt_ctx* c, int ready);

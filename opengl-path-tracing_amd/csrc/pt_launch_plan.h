@@ -39,7 +39,7 @@ constexpr int kMaxSlots = 4, kAutoSlots = 3;
 #endif
 constexpr int kAccumPix = PT_ACCUM_PIX, kAccumPixLong = 2;
 
-// What pt_upload_scene learns about a scene (pt_ctx holds one by value).
+// What ptp::pack_scene (pt_scene_pack.h) learns about a scene (pt_ctx holds one by value).
 struct SceneFacts {
     int n_nodes = 0, n_spheres = 0, n_mats = 0, n_slots = 0, n_top = 0, walk_np = 1, scene_fast = 0;
     // the tree is a full binary tree threaded in preorder whose internal boxes contain their children's

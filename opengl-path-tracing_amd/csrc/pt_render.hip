@@ -7,7 +7,7 @@
 // restatement of those semantics; every float op is pinned via pt_math.h
 // and -ffp-contract=off.
 //
-// Device layouts, built once at pt_upload_scene from the std140 records:
+// Device layouts, built once per upload from the std140 records (pt_scene_pack.cpp):
 //   node  32 B : {min.x, max.x, min.y, max.y}, {min.z, max.z, a, b}   (axis-paired so a
 //                slab axis is one packed-f32 register pair)
 //                internal: a = hit link (left child), b = miss
@@ -25,6 +25,7 @@
 #include "pt_math.h"
 #include "pt_noise.h"
 #include "pt_render_kernels.h"
+#include "pt_scene_pack.h"
 #include "pt_wide.h"
 #include "../../include/pt_api.h"
 #include "../../include/pt_scene.h"
@@ -678,10 +679,7 @@ __device__ __forceinline__ void trav_walk(const SceneView& S, f3 o, f3 d, f3 rd,
 // stride; each alone +0.5 / +2.6% (depth), +1.3 / -0.2% (unroll), +0.5 / +0.3% (stride))
 constexpr int kWideStack = ptw::kStack;   // pt_wide.h (PT_WIDE_STACK)
 // float4 per device record: the three quads of pt_wide.h packed (48 B) or on a 64-B stride
-#ifndef PT_WIDE_STRIDE
-#define PT_WIDE_STRIDE 3
-#endif
-constexpr int kWideStride = PT_WIDE_STRIDE;
+using ptp::kWideStride;                   // pt_scene_pack.h (PT_WIDE_STRIDE)
 #ifndef PT_WIDE_UNROLL
 #define PT_WIDE_UNROLL 3
 #endif
@@ -1532,9 +1530,6 @@ __global__ __launch_bounds__(256) void k_noise(KParams p, int frames, unsigned t
 using ptl::kAutoSlots;
 using ptl::kMaxSlots;
 using ptl::kShortLaunch;
-// global-memory scenes: the first kTopNodes device nodes (breadth-first from the root) are
-// staged in LDS, 24 KiB per workgroup (6 workgroups per CU stay resident)
-constexpr int kTopNodes = 768;
 // Scratch ring of overlapped launches: each launch takes the next entry (colour scratch, queue
 // head, render / accumulate events) of a ring kRingMult times as long as the render streams, so
 // a render waits for the accumulate pass of the launch kRingMult * slots back, not of the one
@@ -1554,15 +1549,9 @@ struct pt_ctx {
     int n_launches = 0;
     float4* accum = nullptr;
     uchar4* rgba8 = nullptr;
-    float4 *d_nodes = nullptr, *d_tris = nullptr, *d_mats = nullptr, *d_spheres = nullptr;
-    float4* d_walk_lds = nullptr;   // LDS walk image (DevScene)
-    float4* d_walk_sk = nullptr;    // ... the culling walk's copy with its sink image
-    ptl::SceneFacts sf;             // what pt_upload_scene learned (the launch planner's input)
+    float4* d_scene[ptp::kBufs] = {};   // the device scene (ptp::SceneBuf); null: the scene has no such buffer
+    ptl::SceneFacts sf;             // what ptp::pack_scene learned (the launch planner's input)
     ptl::Tuning tun;                // pt_set_tuning values and the kernel variant
-    // the wide walk of global-memory scenes (pt_wide.h; nested trees inside the scene guard):
-    // records, exact leaf boxes, and the node / triangle arrays with leaf slots numbered by the
-    // wide tree's index (the binary walk of the lanes outside the guard shares them)
-    float4 *d_wrec = nullptr, *d_wlbox = nullptr, *d_nodesw = nullptr, *d_trisw = nullptr;
     unsigned long long* d_counters = nullptr;
     unsigned int* d_work = nullptr;
     int* d_frame = nullptr;                      // progressive graph frame counter
@@ -1671,12 +1660,10 @@ static int set_tiles(pt_ctx* c, int s) {
 }
 
 static void free_scene(pt_ctx* c) {
-    (void)hipFree(c->d_nodes); (void)hipFree(c->d_tris); (void)hipFree(c->d_mats); (void)hipFree(c->d_spheres);
-    (void)hipFree(c->d_walk_lds);
-    (void)hipFree(c->d_walk_sk);
-    (void)hipFree(c->d_wrec); (void)hipFree(c->d_wlbox); (void)hipFree(c->d_nodesw); (void)hipFree(c->d_trisw);
-    c->d_nodes = c->d_tris = c->d_mats = c->d_spheres = c->d_walk_lds = c->d_walk_sk = nullptr;
-    c->d_wrec = c->d_wlbox = c->d_nodesw = c->d_trisw = nullptr;
+    for (float4*& d : c->d_scene) {
+        (void)hipFree(d);
+        d = nullptr;
+    }
     c->sf.wide_ok = false;
     c->sf.n_wide = 0;
     c->scene_ok = false;
@@ -1778,343 +1765,25 @@ const char* pt_last_error(const pt_ctx* c) { return c ? c->err.c_str() : "null c
 int pt_upload_scene(pt_ctx* c, const float* tris, int n_tris, const float* bvh, int n_nodes,
                     const float* mats, int n_mats, const float* spheres, int n_spheres) {
     if (!c) return PT_E_ARG;
-    if (n_tris < 0 || n_nodes < 0 || n_mats < 0 || n_spheres < 0) return fail(c, PT_E_ARG, "negative count");
-    if ((n_tris && !tris) || (n_nodes && !bvh) || (n_mats && !mats) || (n_spheres && !spheres))
-        return fail(c, PT_E_ARG, "null array with nonzero count");
-    if (n_nodes > (1 << 24) || n_tris > (1 << 24)) return fail(c, PT_E_SCENE, "scene exceeds 2^24 records");
-    if (n_mats == 0 && (n_nodes > 0 || n_spheres > 0)) return fail(c, PT_E_SCENE, "no materials");
+    int rc = ptp::check_scene_args(tris, n_tris, bvh, n_nodes, mats, n_mats, spheres, n_spheres, c->err);
+    if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    // --- validate the threaded BVH (every walk must terminate; leaves hit == miss)
-    std::vector<float4> dn(2 * (size_t)std::max(n_nodes, 1));
-    std::vector<int> leaf_slot(n_nodes, -1);
-    int n_leaves = 0;
-    for (int i = 0; i < n_nodes; i++) {
-        const float* nd = bvh + 12 * (size_t)i;
-        bool leaf = nd[8] > -1.0f;
-        // the shader's int(float) truncates; values outside (-2, n) -- NaN included -- are
-        // rejected before any cast (a float-to-int cast out of range is undefined)
-        const auto in_open = [](float v, float lo, float hi) { return v > lo && v < hi; };
-        if (!in_open(nd[10], -2.0f, (float)n_nodes) || !in_open(nd[11], -2.0f, (float)n_nodes))
-            return fail(c, PT_E_SCENE, "BVH link out of range at node " + std::to_string(i));
-        int hl = (int)nd[10], ml = (int)nd[11];
-        if (leaf) {
-            if (!in_open(nd[8], -1.0f, (float)n_tris) || !in_open(nd[9], -1.0f, (float)n_tris))
-                return fail(c, PT_E_SCENE, "leaf triangle index out of range at node " + std::to_string(i));
-            int t0 = (int)nd[8], t1 = (int)nd[9];
-            if (t0 < 0 || t0 >= n_tris || t1 < 0 || t1 >= n_tris)
-                return fail(c, PT_E_SCENE, "leaf triangle index out of range at node " + std::to_string(i));
-            if (hl != ml) return fail(c, PT_E_SCENE, "leaf with hit link != miss link is unsupported");
-            leaf_slot[i] = n_leaves++;
-        } else if (hl < 0) {
-            return fail(c, PT_E_SCENE, "internal node without a hit link at node " + std::to_string(i));
-        }
-    }
-    // acyclicity of the (hit, miss) link graph reachable from node 0.  The state-machine
-    // kernel relies on it: a walk then visits each node at most once, so the reference's
-    // steps < numNodes bound (:393) cannot bind and no step counter is kept.
-    if (n_nodes > 0) {
-        std::vector<unsigned char> color(n_nodes, 0);
-        std::vector<std::pair<int, int>> st;
-        st.emplace_back(0, 0);
-        color[0] = 1;
-        while (!st.empty()) {
-            auto& top = st.back();
-            const float* nd = bvh + 12 * (size_t)top.first;
-            if (top.second >= 2) { color[top.first] = 2; st.pop_back(); continue; }
-            int nx = (int)nd[10 + top.second];
-            top.second++;
-            if (nx < 0) continue;
-            if (color[nx] == 1) return fail(c, PT_E_SCENE, "BVH links form a cycle");
-            if (color[nx] == 0) { color[nx] = 1; st.emplace_back(nx, 0); }
-        }
-    }
-    for (int i = 0; i < n_tris; i++) {
-        const float fm = tris[16 * (size_t)i + 12];
-        if (!(fm > -1.0f && fm < (float)n_mats)) return fail(c, PT_E_SCENE, "triangle material index out of range");
-    }
-    for (int i = 0; i < n_spheres; i++) {
-        const float fm = spheres[8 * (size_t)i + 4];
-        if (!(fm > -1.0f && fm < (float)n_mats)) return fail(c, PT_E_SCENE, "sphere material index out of range");
-    }
-    // --- device node numbering: the first kTopNodes nodes in breadth-first order of the walk
-    // links from the root (the nodes nearly every walk passes: the global-memory walk keeps
-    // them in LDS, node_at), the rest in their original order.  Links are renumbered with the
-    // nodes, so every walk visits the same node sequence; the root stays node 0.
-    std::vector<int> pos(n_nodes, -1);
-    {
-        int nx = 0;
-        std::vector<int> q;
-        if (n_nodes > 0) { pos[0] = nx++; q.push_back(0); }
-        for (size_t qi = 0; qi < q.size() && nx < kTopNodes; qi++) {
-            const float* nd = bvh + 12 * (size_t)q[qi];
-            for (int l = 10; l < 12; l++) {
-                const int t = (int)nd[l];
-                if (t >= 0 && pos[t] < 0 && nx < kTopNodes) { pos[t] = nx++; q.push_back(t); }
-            }
-        }
-        for (int i = 0; i < n_nodes; i++)
-            if (pos[i] < 0) pos[i] = nx++;
-    }
-    std::vector<int> slot_of(n_nodes, -1);   // leaf slot by device node index
-    std::vector<int> code_of(n_nodes, 0);    // leaf code by reference node index
-    std::vector<unsigned char> cop_of(n_nodes, 0);   // coplanar leaf pair, by reference node index
-    // --- transpose to device layouts
-    std::vector<float4> dt(8 * (size_t)std::max(n_leaves, 1));
-    auto put_tri = [&](float4* q, int ti) {
-        const float* t = tris + 16 * (size_t)ti;
-        f3 v0 = mk(t[0], t[1], t[2]), v1 = mk(t[4], t[5], t[6]), v2 = mk(t[8], t[9], t[10]);
-        f3 n = pt::normalize(pt::cross(v1 - v0, v2 - v0));
-        float d0 = -pt::dot(n, v0);
-        int m = (int)t[12];
-        float mb;
-        std::memcpy(&mb, &m, 4);
-        q[0] = make_float4(n.x, n.y, n.z, d0);      // the plane test reads this quad alone
-        q[1] = make_float4(v0.x, v0.y, v0.z, 0.0f); // .w: the LDS walk's continuation (below)
-        q[2] = make_float4(v1.x, v1.y, v1.z, mb);
-        q[3] = make_float4(v2.x, v2.y, v2.z, 0.0f);
-    };
-    for (int i = 0; i < n_nodes; i++) {
-        const float* nd = bvh + 12 * (size_t)i;
-        int a, b;
-        if (leaf_slot[i] >= 0) {
-            int s = leaf_slot[i];
-            int t0 = (int)nd[8], t1 = (int)nd[9];
-            put_tri(&dt[8 * (size_t)s], t0);
-            put_tri(&dt[8 * (size_t)s + 4], t1);
-            bool cop;
-            {   // coplanar pair: both triangles carry the same (n, d0) up to the sign of zero
-                // components (the two halves of an OBJ quad, a single-triangle leaf's copy),
-                // flagged in the leaf code (bit 1).  hit_triangle's plane distance
-                // -(dot(n,o) + d0) / dot(n,d) is then the same for both wherever it can pass
-                // the leaf's acceptance tests: a zero factor of either sign only changes the
-                // sign of zero intermediate sums, so the two quotients are bitwise equal or
-                // both +-0, +-inf or NaN, which fail t > 1e-4 / t >= 1e-4 alike.  NaN (a
-                // degenerate triangle) never compares equal: such pairs are not flagged.
-                const float4 A = dt[8 * (size_t)s], B = dt[8 * (size_t)s + 4];
-                cop = A.x == B.x && A.y == B.y && A.z == B.z && A.w == B.w;
-            }
-            a = ~((s << 2) | (cop ? 2 : 0) | (t0 == t1 ? 1 : 0));
-            code_of[i] = ~a;
-            cop_of[i] = cop ? 1 : 0;
-            b = (int)nd[11];
-            slot_of[pos[i]] = s;
-        } else {
-            a = pos[(int)nd[10]];
-            b = (int)nd[11];
-        }
-        if (b >= 0) b = pos[b];
-        float fa, fb;
-        std::memcpy(&fa, &a, 4);
-        std::memcpy(&fb, &b, 4);
-        // axis-paired: (min, max) of one axis in adjacent registers for packed-f32 slabs
-        const size_t j = (size_t)pos[i];
-        dn[2 * j] = make_float4(nd[0], nd[4], nd[1], nd[5]);
-        dn[2 * j + 1] = make_float4(nd[2], nd[6], fa, fb);
-    }
-    std::vector<float4> dm(3 * (size_t)std::max(n_mats, 1));
-    for (int i = 0; i < n_mats; i++) {
-        const float* m = mats + 16 * (size_t)i;
-        float s = m[12];
-        dm[3 * (size_t)i] = make_float4(m[0], m[1], m[2], m[13]);
-        dm[3 * (size_t)i + 1] = make_float4(m[4] * s, m[5] * s, m[6] * s, m[14]);
-        dm[3 * (size_t)i + 2] = make_float4(m[8], m[9], m[10], 0.0f);
-    }
-    std::vector<float4> ds(2 * (size_t)std::max(n_spheres, 1));
-    for (int i = 0; i < n_spheres; i++) {
-        const float* s = spheres + 8 * (size_t)i;
-        int m = (int)s[4];
-        float mb;
-        std::memcpy(&mb, &m, 4);
-        ds[2 * (size_t)i] = make_float4(s[0], s[1], s[2], s[3] * s[3]);
-        ds[2 * (size_t)i + 1] = make_float4(mb, 0, 0, 0);
-    }
-    // LDS walk images of the state-machine kernel (WalkLinks in the kernel source): per ray
-    // octant k the node planes (bounds of the axes whose bit is set in k swapped) with links
-    // as byte offsets (16 * (2N * k + index)) and a leaf's hit link -2 - code; the leaf's
-    // next-right (image-0 offset) goes to its first triangle's quad 1 .w
-    const size_t N = (size_t)(n_nodes <= kPadNodes ? kPadNodes : n_nodes);   // nodes per image plane
-    std::vector<float4> dwl(16 * N, make_float4(0, 0, 0, 0));
-    for (int k = 0; k < 8; k++) {
-        const int base = 16 * 2 * (int)N * k;
-        for (int i = 0; i < n_nodes; i++) {
-            float4 lo = dn[2 * (size_t)i], hi = dn[2 * (size_t)i + 1];
-            int a, b;
-            std::memcpy(&a, &hi.z, 4);
-            std::memcpy(&b, &hi.w, 4);
-            const bool leaf = a < 0;
-            int ha = leaf ? -2 - ~a : base + 16 * a, hb = b >= 0 ? base + 16 * b : -1;
-            std::memcpy(&hi.z, &ha, 4);
-            std::memcpy(&hi.w, &hb, 4);
-            if (k & 1) std::swap(lo.x, lo.y);
-            if (k & 2) std::swap(lo.z, lo.w);
-            if (k & 4) std::swap(hi.x, hi.y);
-            dwl[2 * N * k + i] = lo;
-            dwl[2 * N * k + N + i] = hi;
-            if (leaf && k == 0) {
-                std::memcpy(&dt[8 * (size_t)slot_of[i] + 1].w, &hb, 4);
-                const int self = 16 * i;           // the culling walk's exact leaf re-test
-                std::memcpy(&dt[8 * (size_t)slot_of[i] + 7].w, &self, 4);
-            }
-        }
-    }
-    // The culling walk's copy of the walk images: the 8 octant images plus a
-    // ninth of "sinks" -- node records whose links both point to themselves.  A leaf's hit link
-    // leads to its sink (index 1 + k for leaf pair k) and the chain's end (-1) to sink 0, so a
-    // lane that stopped keeps stepping in place: the walk step needs no exec mask, and a lane
-    // walks while its position lies below the sink image.  A leaf's coplanar flag moves to
-    // slot 2k+1 quad 1 .w (the sink index carries only k).
-    std::vector<float4> dsk;
-    const bool nested = pt_bvh_culling_ok(bvh, n_nodes) == 1;   // pt_scene.cpp
-    if (nested) {
-        dsk.assign(18 * N, make_float4(0, 0, 0, 0));
-        std::copy(dwl.begin(), dwl.end(), dsk.begin());
-        const int sink0 = 16 * 2 * (int)N * 8;
-        for (int k = 0; k < 8; k++) {
-            for (int i = 0; i < n_nodes; i++) {
-                float4& hi = dsk[2 * N * k + N + i];
-                int a, b;
-                std::memcpy(&a, &hi.z, 4);
-                std::memcpy(&b, &hi.w, 4);
-                if (a <= -2) a = sink0 + 16 * (1 + ((-2 - a) >> 2));
-                if (b == -1) b = sink0;
-                std::memcpy(&hi.z, &a, 4);
-                std::memcpy(&hi.w, &b, 4);
-            }
-        }
-        for (int i = 0; i <= n_leaves; i++) {
-            const int self = sink0 + 16 * i;
-            float4 hi = make_float4(0, 0, 0, 0);
-            std::memcpy(&hi.z, &self, 4);
-            std::memcpy(&hi.w, &self, 4);
-            dsk[16 * N + N + i] = hi;
-        }
-        for (int i = 0; i < n_nodes; i++) {
-            const float* nd = bvh + 12 * (size_t)i;
-            if (!(nd[8] > -1.0f)) continue;
-            const int cop = (code_of[i] >> 1) & 1;
-            std::memcpy(&dt[8 * (size_t)leaf_slot[i] + 5].w, &cop, 4);
-        }
-    }
-    // The wide tree of the global-memory walk (pt_wide.h): nested trees only
-    // (the superset argument), built whatever the scene size -- variant 3 sends any scene to
-    // the global walk.  Its index g numbers records and leaves; leaf g's triangles go to slots
-    // 2g, 2g + 1 of a second triangle array and its exact box to wlbox[2g], and a second copy
-    // of the device nodes carries leaf codes g << 2 | coplanar << 1 | single for the binary
-    // walk of the lanes outside the guard.
-    ptw::WideTree wt;
-    std::vector<float4> dnw, dtw;
-    const bool wide = nested && ptw::wide_build(bvh, n_nodes, cop_of.data(), wt) == 0;
-    if (wide) {
-        dnw = dn;
-        dtw.assign(8 * (size_t)wt.n_index, make_float4(0, 0, 0, 0));
-        for (int i = 0; i < n_nodes; i++) {
-            const float* nd = bvh + 12 * (size_t)i;
-            if (!(nd[8] > -1.0f)) continue;
-            const int g = wt.g_of[i], t0 = (int)nd[8], t1 = (int)nd[9];
-            // a leaf no walk reaches (not in the nested tree from the root, which is all the
-            // links of reachable nodes lead to) has no index: nothing to place
-            if (g < 0) continue;
-            const int a = ~((g << 2) | (cop_of[i] ? 2 : 0) | (t0 == t1 ? 1 : 0));
-            std::memcpy(&dnw[2 * (size_t)pos[i] + 1].z, &a, 4);
-            put_tri(&dtw[8 * (size_t)g], t0);
-            put_tri(&dtw[8 * (size_t)g + 4], t1);
-
-        }
-    }
+    // validation and every device layout (pt_scene_pack.cpp); a rejected scene leaves the current one in place
+    ptp::PackedScene packed;
+    rc = ptp::pack_scene(tris, n_tris, bvh, n_nodes, mats, n_mats, spheres, n_spheres, packed, c->err);
+    if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));   // a render in flight may still read the old scene
     drop_graph(c);
     free_scene(c);
-    if (wide) {
-        const size_t nr = (size_t)wt.n_index;
-        HIPCHK(c, hipMalloc(&c->d_wrec, nr * kWideStride * sizeof(float4)));
-        HIPCHK(c, hipMalloc(&c->d_wlbox, nr * 2 * sizeof(float4)));
-        HIPCHK(c, hipMalloc(&c->d_nodesw, dnw.size() * sizeof(float4)));
-        HIPCHK(c, hipMalloc(&c->d_trisw, dtw.size() * sizeof(float4)));
-        if (kWideStride != 4) {   // pack the three used quads of each 64-B host record
-            std::vector<float> packed(nr * kWideStride * 4);
-            for (size_t i = 0; i < nr; i++)
-                std::memcpy(&packed[i * kWideStride * 4], &wt.rec[i * 16], kWideStride * 16);
-            wt.rec.swap(packed);
-        }
-        HIPCHK(c, hipMemcpy(c->d_wrec, wt.rec.data(), nr * kWideStride * sizeof(float4), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(c->d_wlbox, wt.lbox.data(), nr * 2 * sizeof(float4), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(c->d_nodesw, dnw.data(), dnw.size() * sizeof(float4), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(c->d_trisw, dtw.data(), dtw.size() * sizeof(float4), hipMemcpyHostToDevice));
-        c->sf.n_wide = wt.n_index;
-        std::memcpy(c->sf.wide_cw, wt.cw, sizeof(c->sf.wide_cw));
+    for (int b = 0; b < ptp::kBufs; b++) {
+        const size_t bytes = packed.buf[b].size() * sizeof(float);
+        if (!bytes) continue;
+        HIPCHK(c, hipMalloc(&c->d_scene[b], bytes));
+        HIPCHK(c, hipMemcpy(c->d_scene[b], packed.buf[b].data(), bytes, hipMemcpyHostToDevice));
     }
-    if (nested) {
-        HIPCHK(c, hipMalloc(&c->d_walk_sk, dsk.size() * sizeof(float4)));
-        HIPCHK(c, hipMemcpy(c->d_walk_sk, dsk.data(), dsk.size() * sizeof(float4), hipMemcpyHostToDevice));
-    }
-    HIPCHK(c, hipMalloc(&c->d_walk_lds, dwl.size() * sizeof(float4)));
-    HIPCHK(c, hipMemcpy(c->d_walk_lds, dwl.data(), dwl.size() * sizeof(float4), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMalloc(&c->d_nodes, dn.size() * sizeof(float4)));
-    HIPCHK(c, hipMalloc(&c->d_tris, dt.size() * sizeof(float4)));
-    HIPCHK(c, hipMalloc(&c->d_mats, dm.size() * sizeof(float4)));
-    HIPCHK(c, hipMalloc(&c->d_spheres, ds.size() * sizeof(float4)));
-    HIPCHK(c, hipMemcpy(c->d_nodes, dn.data(), dn.size() * sizeof(float4), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_tris, dt.data(), dt.size() * sizeof(float4), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_mats, dm.data(), dm.size() * sizeof(float4), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_spheres, ds.data(), ds.size() * sizeof(float4), hipMemcpyHostToDevice));
-    c->sf.n_nodes = n_nodes;
-    c->sf.n_spheres = n_spheres;
-    c->sf.n_mats = n_mats;
-    c->sf.n_slots = 2 * n_leaves;
-    c->sf.n_top = std::min(n_nodes, kTopNodes);
-    // exact-reciprocal slab guard, scene half: every box coordinate is 0
-    // or has magnitude in [2^-40, 2^60], and min <= max on every axis (the octant images'
-    // near-first order, slab_oct)
-    c->sf.scene_fast = 1;
-    for (int i = 0; i < n_nodes && c->sf.scene_fast; i++) {
-        const float* nd = bvh + 12 * (size_t)i;
-        for (int q = 0; q < 7; q++) {
-            if (q == 3) continue;
-            float a = std::fabs(nd[q]);
-            if (!(nd[q] == 0.0f || (a >= 0x1p-40f && a <= 0x1p60f))) { c->sf.scene_fast = 0; break; }
-        }
-        if (!(nd[0] <= nd[4] && nd[1] <= nd[5] && nd[2] <= nd[6])) c->sf.scene_fast = 0;
-    }
-    c->sf.walk_nested = nested;
-    c->sf.wide_ok = wide;
-    // the leaf re-test certificate (ptw::leaf_certificate) needs each leaf box to contain its
-    // triangles' vertices -- the reference builder expands leaf boxes over them (bvh.h:29-52);
-    // an uploaded tree is checked, not assumed
-    c->sf.leaf_cert_ok = true;
-    for (int i = 0; i < n_nodes && c->sf.leaf_cert_ok; i++) {
-        const float* nd = bvh + 12 * (size_t)i;
-        if (!(nd[8] > -1.0f)) continue;
-        for (int k = 0; k < 2 && c->sf.leaf_cert_ok; k++) {
-            const float* t = tris + 16 * (size_t)(int)nd[8 + k];
-            for (int v = 0; v < 3; v++)
-                for (int q = 0; q < 3; q++)
-                    if (!(nd[q] <= t[4 * v + q] && t[4 * v + q] <= nd[4 + q])) c->sf.leaf_cert_ok = false;
-        }
-    }
-    // the window clause of the culling walk (pt_cull.h): its lemma needs the leaf boxes to contain
-    // their triangles and every triangle inside the conditions window_slack checks
-    c->sf.win_slack[0] = c->sf.win_slack[1] = c->sf.win_slack[2] = 0.0f;
-    c->sf.win_bad = !(nested && c->sf.leaf_cert_ok && ptc::window_slack(bvh, n_nodes, tris, c->sf.win_slack));
+    c->sf = packed.facts;
     c->order_sorted = false;      // the next sort pools the new scene's first short launches
     c->order_skip = 0;
-    if (n_nodes > 0) {   // every box lies in the root box (nested): M_i bounds each |coordinate|
-        for (int q = 0; q < 3; q++) {
-            const double m = std::max(std::fabs((double)bvh[q]), std::fabs((double)bvh[4 + q]));
-            c->sf.cons_m[q] = (float)std::ldexp(m * (1.0 + 0x1p-20), -19);   // rounded: within 2^-24 relative
-        }
-    }
-    c->sf.walk_np = (int)N;
-    c->sf.lds_bytes = (size_t)(16 * N + 4 * c->sf.n_slots + 3 * n_mats + 2 * n_spheres) * sizeof(float4);
-    c->sf.lds_bytes_sk = c->sf.lds_bytes + 2 * N * sizeof(float4);
-    c->sf.root_child = -1;
-    if (n_nodes > 0) {
-        const float4 r0 = dn[0], r1 = dn[1];
-        const float box[6] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y};
-        std::memcpy(c->sf.root_box, box, sizeof(box));
-        int a;
-        std::memcpy(&a, &r1.z, 4);
-        c->sf.root_child = a >= 0 ? a : -1;
-    }
     c->scene_ok = true;
     return PT_OK;
 }
@@ -2379,8 +2048,10 @@ static KParams fill_params(const pt_ctx* c, const ptl::LaunchPlan& pl, int frame
     KParams p;
     std::memset(&p, 0, sizeof(p));
     // the wide walk reads the node / triangle arrays numbered by its index, and its records
-    p.sc = {pl.wide ? c->d_nodesw : c->d_nodes, c->d_walk_lds, c->d_walk_sk, pl.wide ? c->d_trisw : c->d_tris,
-            c->d_mats, c->d_spheres, pl.wide ? c->d_wrec : nullptr, pl.wide ? c->d_wlbox : nullptr,
+    float4* const* d = c->d_scene;
+    p.sc = {d[pl.wide ? ptp::kWideNodes : ptp::kNodes], d[ptp::kWalk], d[ptp::kWalkSink],
+            d[pl.wide ? ptp::kWideTris : ptp::kTris], d[ptp::kMats], d[ptp::kSpheres],
+            pl.wide ? d[ptp::kWideRec] : nullptr, pl.wide ? d[ptp::kWideLeafBox] : nullptr,
             c->sf.n_nodes, c->sf.n_spheres};
     if (pl.wide) std::memcpy(p.wide_cw, c->sf.wide_cw, sizeof(p.wide_cw));
     fill_image(p, c);
@@ -2700,28 +2371,19 @@ int pt_get_config(const pt_ctx* c, pt_config* out) {
 // buffers of the same sizes, contents undefined -- and returns both contexts' buffer pointers
 // and sizes, so the caller can fill dst's from src's (an RCCL broadcast across devices or a
 // device copy).  Both contexts must have the same width (tile facts are per image).
-int pt__scene_replicate_layout(pt_ctx* dst, const pt_ctx* src, void* dptr[10], const void* sptr[10],
-                               size_t bytes[10]) {
+int pt__scene_replicate_layout(pt_ctx* dst, const pt_ctx* src, void* dptr[ptp::kBufs], const void* sptr[ptp::kBufs],
+                               size_t bytes[ptp::kBufs]) {
     if (!dst || !src || !dptr || !sptr || !bytes) return PT_E_ARG;
     if (!src->scene_ok) return fail(dst, PT_E_STATE, "source context has no scene");
     HIPCHK(dst, hipSetDevice(dst->cfg.device));
     HIPCHK(dst, hipStreamSynchronize(dst->stream));
     drop_graph(dst);
     free_scene(dst);
-    const size_t nd = 2 * (size_t)std::max(src->sf.n_nodes, 1), nt = 8 * (size_t)std::max(src->sf.n_slots / 2, 1);
-    const size_t nm = 3 * (size_t)std::max(src->sf.n_mats, 1), ns = 2 * (size_t)std::max(src->sf.n_spheres, 1);
-    const size_t nw = 16 * (size_t)src->sf.walk_np, nk = src->d_walk_sk ? 18 * (size_t)src->sf.walk_np : 0;
-    const size_t ni = src->sf.wide_ok ? (size_t)src->sf.n_wide : 0;   // the wide walk's arrays (pt_wide.h)
-    const size_t sz[10] = {nd, nt, nm, ns, nw, nk, kWideStride * ni, 2 * ni, ni ? nd : 0, 8 * ni};
-    float4** mine[10] = {&dst->d_nodes, &dst->d_tris, &dst->d_mats, &dst->d_spheres, &dst->d_walk_lds, &dst->d_walk_sk,
-                         &dst->d_wrec, &dst->d_wlbox, &dst->d_nodesw, &dst->d_trisw};
-    const float4* theirs[10] = {src->d_nodes, src->d_tris, src->d_mats, src->d_spheres, src->d_walk_lds, src->d_walk_sk,
-                                src->d_wrec, src->d_wlbox, src->d_nodesw, src->d_trisw};
-    for (int i = 0; i < 10; i++) {
-        bytes[i] = sz[i] * sizeof(float4);
-        sptr[i] = theirs[i];
-        if (sz[i]) HIPCHK(dst, hipMalloc(mine[i], bytes[i]));
-        dptr[i] = *mine[i];
+    for (int i = 0; i < ptp::kBufs; i++) {
+        bytes[i] = ptp::buf_quads(src->sf, i) * sizeof(float4);
+        sptr[i] = src->d_scene[i];
+        if (bytes[i]) HIPCHK(dst, hipMalloc(&dst->d_scene[i], bytes[i]));
+        dptr[i] = dst->d_scene[i];
     }
     dst->sf = src->sf;
     dst->order_sorted = false;
@@ -2744,7 +2406,7 @@ int pt__aces_launch(const void* src, void* dst, long long n, void* stream) {
 
 int pt__scene_set_ready(pt_ctx* c, int ready) {
     if (!c) return PT_E_ARG;
-    c->scene_ok = ready != 0 && c->d_mats != nullptr;
+    c->scene_ok = ready != 0 && c->d_scene[ptp::kMats] != nullptr;
     return PT_OK;
 }
 

@@ -15,6 +15,7 @@
 // Exit status 0 = no violation, 3 = the tree does not qualify for the culling walk.
 // Output: one JSON line of statistics.
 #include "../../opengl-path-tracing_amd/csrc/pt_cull.h"
+#include "../../opengl-path-tracing_amd/csrc/pt_scene_pack.h"
 
 #include <cmath>
 #include <cstdio>
@@ -231,21 +232,16 @@ int main(int argc, char** argv) {
     const int stride = argc > 2 ? std::atoi(argv[2]) : 16;
     const int bounces = argc > 3 ? std::atoi(argv[3]) : 8;
     const long adversarial = argc > 4 ? std::atol(argv[4]) : 0;
-    // the conditions of pt_upload_scene: a full binary tree threaded in preorder whose boxes nest
-    // (parents from the links: an internal node's children are its hit link and that child's miss
-    // link), and leaf boxes that contain their triangles' vertices
+    // a full binary tree threaded in preorder whose boxes nest, with the parents the ancestor checks need (parents
+    // from the links: an internal node's children are its hit link and that child's miss link) -- the sim's own
+    // restatement of pt_bvh_culling_ok, which keeps no parents
     parent.assign(nn, -1);
-    bool nested = true, leaf_ok = true;
+    bool nested = true;
     for (int i = 0; i < nn && nested; i++) {
         const float* b = &nodes[12 * (size_t)i];
         if (b[8] > -1.0f) {
-            for (int k = 0; k < 2; k++) {
-                const int ti = (int)b[8 + k];
-                if (ti < 0 || ti >= nt) { nested = false; break; }
-                for (int v = 0; v < 3; v++)
-                    for (int q = 0; q < 3; q++)
-                        if (!(b[q] <= tris[16 * (size_t)ti + 4 * v + q] && tris[16 * (size_t)ti + 4 * v + q] <= b[4 + q])) leaf_ok = false;
-            }
+            for (int k = 0; k < 2; k++)
+                if (!(b[8 + k] > -1.0f && b[8 + k] < (float)nt)) nested = false;
             continue;
         }
         const int l = (int)b[10];
@@ -265,12 +261,10 @@ int main(int argc, char** argv) {
         std::printf("{\"nested\": false}\n");
         return 3;
     }
-    for (int q = 0; q < 3; q++) {   // KParams::cons_m as pt_upload_scene rounds it
-        const double m = std::fmax(std::fabs((double)nodes[q]), std::fabs((double)nodes[4 + q]));
-        cm[q] = (float)std::ldexp(m * (1.0 + 0x1p-20), -19);
-    }
-    const bool win_ok = leaf_ok && ptc::window_slack(nodes.data(), nn, tris.data(), ws);
-    if (!win_ok) ws[0] = ws[1] = ws[2] = 0.0f;
+    // the scene facts of the upload (pt_scene_pack.h): KParams::cons_m, the leaf containment and the window slack
+    ptp::cons_margin(nodes.data(), cm);
+    const bool win_ok = ptp::window_clause(true, ptp::leaves_contain_tris(nodes.data(), nn, tris.data()), nodes.data(), nn,
+                                           tris.data(), ws);
     c_lo_on = win_ok ? ptc::kWindowLo : kNoWindow;   // a scene outside the lemma's conditions runs without the clause
 
     // diffuse paths: camera basis (computeShader.c:517-522), 1920x1080 grid sampled every `stride` pixels

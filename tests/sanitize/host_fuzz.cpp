@@ -1,8 +1,10 @@
 // host_fuzz.cpp -- ASan + UBSan driver for the host-side ingest of the drop-in library
 // (csrc/pt_scene.cpp, csrc/pt_viewer.cpp): the OBJ/MTL loaders (reference and robust modes,
 // geometry_loader.h:15-142), the SAH builder (bvh.h:173-268), the culling-walk tree check and
-// the headless viewer controller (ogl_path_trace.h:258-364), and the wide tree builder of the
-// global-memory walk (pt_wide.cpp) on every accepted tree and the random ones.  Test infrastructure only: built
+// the headless viewer controller (ogl_path_trace.h:258-364), the wide tree builder of the
+// global-memory walk (pt_wide.cpp) on the random trees, and the scene packer (pt_scene_pack.cpp:
+// validation and every device layout) on every accepted scene and on random and mutated node
+// arrays.  Test infrastructure only: built
 // by tests/sanitize/Makefile with -fsanitize=address,undefined -fno-sanitize-recover, run by
 // tests/test_sanitize.py; any report aborts the process.
 //
@@ -14,6 +16,7 @@
 #include "../../include/pt_api.h"
 #include "../../include/pt_scene.h"
 #include "../../include/pt_viewer.h"
+#include "../../opengl-path-tracing_amd/csrc/pt_scene_pack.h"
 #include "../../opengl-path-tracing_amd/csrc/pt_wide.h"
 
 #include <cmath>
@@ -60,7 +63,22 @@ std::string read_file(const char* path) {
     return s;
 }
 
-int g_ok = 0, g_err = 0;
+int g_ok = 0, g_err = 0, g_packed = 0, g_refused = 0;
+
+// The upload's host half: PT_OK or a refusal, never a sanitizer report; what it packs has the sizes
+// the facts promise (pack_scene asserts it).
+bool pack(const std::vector<float>& tris, const std::vector<float>& nodes, const std::vector<float>& mats,
+          const std::vector<float>& sph, ptp::PackedScene& ps) {
+    std::string err;
+    const int rc = ptp::pack_scene(tris.data(), (int)(tris.size() / 16), nodes.data(), (int)(nodes.size() / 12), mats.data(),
+                                   (int)(mats.size() / 16), sph.data(), (int)(sph.size() / 8), ps, err);
+    if (rc != PT_OK && rc != PT_E_SCENE) { std::fprintf(stderr, "pack_scene: bad status %d\n", rc); std::abort(); }
+    (rc == PT_OK ? g_packed : g_refused)++;
+    return rc == PT_OK;
+}
+
+// the first small accepted scene, for fuzz_nodes to mutate
+std::vector<float> g_tris, g_nodes, g_mats, g_sph;
 
 // Load (both modes), add built-ins, build, copy out, check the tree; every status must be
 // 0 or a PT_E* code.
@@ -81,17 +99,23 @@ void exercise(const char* obj, const char* mtl) {
         if (pt_scene_counts(s, cnt) == 0 && cnt[0] > 0 && cnt[0] < (1 << 16)) {
             if (pt_scene_build_bvh(s) == 0) {
                 pt_scene_counts(s, cnt);
-                std::vector<float> nodes((size_t)cnt[3] * 12), tris((size_t)cnt[0] * 16);
+                std::vector<float> nodes((size_t)cnt[3] * 12), tris((size_t)cnt[0] * 16), mats((size_t)cnt[1] * 16),
+                    sph((size_t)cnt[2] * 8);
                 pt_scene_get_nodes(s, nodes.data(), cnt[3]);
                 pt_scene_get_tris(s, tris.data(), cnt[0]);
-                if (pt_bvh_culling_ok(nodes.data(), cnt[3]) == 1) {   // pt_upload_scene's wide build
-                    ptw::WideTree wt;
-                    std::vector<unsigned char> cop((size_t)cnt[3], 0);
-                    if (ptw::wide_build(nodes.data(), cnt[3], cop.data(), wt) != 0) {
-                        std::fprintf(stderr, "wide_build refused a nested tree\n");
-                        std::abort();
-                    }
+                pt_scene_get_mats(s, mats.data(), cnt[1]);
+                pt_scene_get_spheres(s, sph.data(), cnt[2]);
+                ptp::PackedScene ps;   // pt_upload_scene's host half; the builder's trees are nested
+                const bool packed = pack(tris, nodes, mats, sph, ps);
+                if (!packed && cnt[1] > 0) {
+                    std::fprintf(stderr, "pack_scene refused a loaded and built scene\n");
+                    std::abort();
                 }
+                if (packed && pt_bvh_culling_ok(nodes.data(), cnt[3]) == 1 && !ps.facts.wide_ok) {
+                    std::fprintf(stderr, "wide_build refused a nested tree\n");
+                    std::abort();
+                }
+                if (g_nodes.empty() && cnt[3] <= 256) { g_tris = tris; g_nodes = nodes; g_mats = mats; g_sph = sph; }
                 std::vector<float> n2((size_t)(2 * cnt[0]) * 12);
                 int nn = 0;
                 pt_bvh_build(tris.data(), cnt[0], n2.data(), 2 * cnt[0], &nn);
@@ -153,21 +177,36 @@ std::string mutate(const std::string& base) {
     return s;
 }
 
-// Random node arrays: garbage links, NaNs, huge values, partial trees.
+float fuzz_value(int n) {
+    switch (rnd() % 8) {
+    case 0: return NAN;
+    case 1: return INFINITY;
+    case 2: return 3e38f;
+    case 3: return -1.0f;
+    case 4: return (float)(rnd() % (unsigned)(n + 2)) - 1.0f;
+    case 5: return 0.5f;
+    default: return (float)(int)(rnd() % 64) - 8.0f;
+    }
+}
+
+// Random node arrays: garbage links, NaNs, huge values, partial trees; and an accepted scene's
+// nodes with a few such values written over them (most of the tree stays valid, so the packer
+// gets past its validation with boxes, links and leaf indices it did not expect).
 void fuzz_nodes(int iters) {
+    ptp::PackedScene ps;
     for (int it = 0; it < iters; it++) {
         const int n = 1 + (int)(rnd() % 40);
         std::vector<float> nd((size_t)n * 12);
-        for (auto& x : nd) {
-            switch (rnd() % 8) {
-            case 0: x = NAN; break;
-            case 1: x = INFINITY; break;
-            case 2: x = 3e38f; break;
-            case 3: x = -1.0f; break;
-            case 4: x = (float)(rnd() % (unsigned)(n + 2)) - 1.0f; break;
-            case 5: x = 0.5f; break;
-            default: x = (float)(int)(rnd() % 64) - 8.0f; break;
+        for (auto& x : nd) x = fuzz_value(n);
+        pack(g_tris, nd, g_mats, g_sph, ps);
+        if (!g_nodes.empty()) {
+            std::vector<float> mut = g_nodes;
+            const int nm = (int)(mut.size() / 12);
+            for (int e = 1 + (int)(rnd() % 3); e > 0; e--) {
+                const size_t at = rnd() % mut.size();
+                mut[at] = (rnd() & 1) ? fuzz_value(nm) : mut[at] + ((rnd() & 1) ? 1.0f : -0.75f);
             }
+            pack(g_tris, mut, g_mats, g_sph, ps);
         }
         const int r = pt_bvh_culling_ok(nd.data(), n);
         if (r != 0 && r != 1) std::abort();
@@ -243,6 +282,7 @@ int main(int argc, char** argv) {
     std::vector<float> px = {0.f, 1.f, NAN, INFINITY, -1.f, 1e30f, 0.5f, 2.f};
     unsigned char out[8];
     pt_aces_rgba8_host(px.data(), 2, out);
-    std::printf("host_fuzz ok: %d loads accepted, %d rejected, %d iterations\n", g_ok, g_err, iters);
+    std::printf("host_fuzz ok: %d loads accepted, %d rejected, %d iterations; %d scenes packed, %d refused\n", g_ok, g_err,
+                iters, g_packed, g_refused);
     return 0;
 }

@@ -8,6 +8,9 @@ tests/sanitize/host_fuzz.cpp links csrc/pt_scene.cpp and csrc/pt_viewer.cpp with
   * the SAH builder (bvh.h:173-268) on every accepted scene, twice (scene object and raw
     arrays, which must agree), and an undersized node buffer, which must be refused;
   * pt_bvh_culling_ok on random node arrays (NaN / huge link floats);
+  * the scene packer (csrc/pt_scene_pack.cpp: pt_upload_scene's validation and every device layout) on every
+    accepted scene, on those random node arrays and on an accepted tree's nodes with such values written over a
+    few of them, which it must refuse or pack;
   * the headless viewer (ogl_path_trace.h:258-364) on random key / cursor / clock events.
 Any sanitizer report aborts the process.  No GPU needed.
 """

@@ -12,6 +12,7 @@
 //   scene.bin: int32 n_tris, n_nodes, n_spheres, then float32 tris (16 per), nodes (12 per),
 //   spheres (8 per), camera (12: pos, dir, 0...) -- written by tests/test_wide_walk.py.
 // Exit status 0 = no mismatch.  Output: one JSON line of statistics.
+#include "../../opengl-path-tracing_amd/csrc/pt_scene_pack.h"
 #include "../../opengl-path-tracing_amd/csrc/pt_wide.h"
 
 #include <cmath>
@@ -91,7 +92,7 @@ bool leaf_choice(int bnode, f3 o, f3 d, float t, float& nt_, int& ntri) {
 }
 
 struct RefOut { float t; int tri; long visits, leaves, top; };
-std::vector<unsigned char> ref_top_set;   // the binary walk's LDS top nodes (768 breadth-first)
+std::vector<unsigned char> ref_top_set;   // the binary walk's LDS top nodes (ptp::top_numbering)
 RefOut ref_walk(f3 o, f3 d, float t0) {
     RefOut r{t0, -1, 0, 0, 0};
     for (int bi = 0; bi > -1;) {
@@ -235,31 +236,17 @@ int main(int argc, char** argv) {
     const int bounces = argc > 3 ? std::atoi(argv[3]) : 8;
     const long adversarial = argc > 4 ? std::atol(argv[4]) : 0;
     if (argc > 5) top_records = std::atoi(argv[5]);
-    // the leaf flags of pt_upload_scene: both triangles' (n, d0) equal
+    // the leaf flags and the LDS top set of the upload (pt_scene_pack.h).  In a tree of at most kTopNodes nodes the
+    // set also holds the nodes no link reaches, which no walk visits: the `top` statistic does not see them.
     std::vector<unsigned char> cop(nn, 0);
     for (int i = 0; i < nn; i++) {
         const float* b = &nodes[12 * (size_t)i];
         if (!(b[8] > -1.0f)) continue;
-        float nd[2][4];
-        for (int k = 0; k < 2; k++) {
-            const float* tr = &tris[16 * (size_t)(int)b[8 + k]];
-            const f3 v0 = ld3(tr), v1 = ld3(tr + 4), v2 = ld3(tr + 8);
-            const f3 n = pt::normalize(pt::cross(v1 - v0, v2 - v0));
-            nd[k][0] = n.x; nd[k][1] = n.y; nd[k][2] = n.z; nd[k][3] = -pt::dot(n, v0);
-        }
-        cop[i] = nd[0][0] == nd[1][0] && nd[0][1] == nd[1][1] && nd[0][2] == nd[1][2] && nd[0][3] == nd[1][3];
+        cop[i] = ptp::same_plane(ptp::tri_plane(&tris[16 * (size_t)(int)b[8]]), ptp::tri_plane(&tris[16 * (size_t)(int)b[9]]));
     }
-    {   // pt_upload_scene's breadth-first top numbering (kTopNodes = 768)
-        ref_top_set.assign(nn, 0);
-        std::vector<int> q{0};
-        ref_top_set[0] = 1;
-        int cnt = 1;
-        for (size_t qi = 0; qi < q.size() && cnt < 768; qi++)
-            for (int l = 10; l < 12; l++) {
-                const int t = (int)nodes[12 * (size_t)q[qi] + l];
-                if (t >= 0 && !ref_top_set[t] && cnt < 768) { ref_top_set[t] = 1; cnt++; q.push_back(t); }
-            }
-    }
+    ref_top_set.assign(nn, 0);
+    const std::vector<int> top = ptp::top_numbering(nodes.data(), nn);
+    for (int i = 0; i < nn; i++) ref_top_set[i] = top[i] < ptp::kTopNodes;
     if (ptw::wide_build(nodes.data(), nn, cop.data(), W) != 0) {
         std::printf("{\"built\": false}\n");
         return 3;
