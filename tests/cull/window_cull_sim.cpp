@@ -1,8 +1,9 @@
 // TEST INFRASTRUCTURE: CPU model of the LDS culling walk with its window clause (pt_cull.h,
 // DESIGN.md §5.6) against the reference's binary32 walk (calculateRayCollision,
-// computeShader.c:367-432; bvh_intersect :309-365; hit_triangle :274-307).  It runs the SAME
-// node test, per-ray addends and window slack the kernel and pt_upload_scene use
-// (ptc::cull_hit / cull_addends / window_slack, compiled for the host) and fails on
+// computeShader.c:367-432; bvh_intersect :309-365; hit_triangle :274-307; tests/ref_walk.h).  It
+// runs the SAME node test, leaf re-test, per-ray addends and window slack the kernel and
+// pt_upload_scene use (pti::slab_oct_cons / slab_oct, ptc::cull_addends / window_slack, compiled
+// for the host) and fails on
 //   (a) a segment whose final t (bitwise) or triangle differs from the reference's,
 //   (b) a leaf at which the reference accepts a triangle while the culling test (with the
 //       clause) rejects that leaf or one of its ancestors at the t of that moment,
@@ -15,7 +16,9 @@
 // Exit status 0 = no violation, 3 = the tree does not qualify for the culling walk.
 // Output: one JSON line of statistics.
 #include "../../opengl-path-tracing_amd/csrc/pt_cull.h"
+#include "../../opengl-path-tracing_amd/csrc/pt_isect.h"
 #include "../../opengl-path-tracing_amd/csrc/pt_scene_pack.h"
+#include "../ref_walk.h"
 
 #include <cmath>
 #include <cstdio>
@@ -26,88 +29,37 @@
 
 using pt::f3;
 using pt::mk;
+using namespace ref;   // the scene and the reference side
 
 namespace {
 
-std::vector<float> tris, nodes, sph;
 std::vector<int> parent;
-int nt = 0, nn = 0, ns = 0;
-float cam[12], cm[3], ws[3] = {0, 0, 0};
+float cm[3], ws[3] = {0, 0, 0};
 
-// computeShader.c:309-365 in IEEE division (the reference's exact test)
-bool slab_exact(const float* lo, const float* hi, f3 o, f3 d, float cur_t) {
-    float tmin = (lo[0] - o.x) / d.x, tmax = (hi[0] - o.x) / d.x;
-    if (tmin > tmax) std::swap(tmin, tmax);
-    float tymin = (lo[1] - o.y) / d.y, tymax = (hi[1] - o.y) / d.y;
-    if (tymin > tymax) std::swap(tymin, tymax);
-    if ((tmin > tymax) || (tymin > tmax)) return false;
-    if (tymin > tmin) tmin = tymin;
-    if (tymax < tmax) tmax = tymax;
-    float tzmin = (lo[2] - o.z) / d.z, tzmax = (hi[2] - o.z) / d.z;
-    if (tzmin > tzmax) std::swap(tzmin, tzmax);
-    if ((tmin > tzmax) || (tzmin > tmax)) return false;
-    if (tzmin > tmin) tmin = tzmin;
-    return !(tmin > cur_t);
-}
-bool node_exact(int i, f3 o, f3 d, float t) {
-    const float* b = &nodes[12 * (size_t)i];
-    return slab_exact(b, b + 4, o, d, t);
-}
-
-f3 ld3(const float* p) { return mk(p[0], p[1], p[2]); }
-
-// :274-307
-float hit_triangle(f3 o, f3 d, int ti) {
-    const float* tr = &tris[16 * (size_t)ti];
-    const f3 v0 = ld3(tr), v1 = ld3(tr + 4), v2 = ld3(tr + 8);
-    const f3 n = pt::normalize(pt::cross(v1 - v0, v2 - v0));
-    const float dd = -pt::dot(n, v0);
-    const float t = -(pt::dot(n, o) + dd) / pt::dot(n, d);
-    if (t < 0.0f) return -1.0f;
-    const f3 p = o + d * t;
-    if (pt::dot(n, pt::cross(v1 - v0, p - v0)) > 0.0f && pt::dot(n, pt::cross(v2 - v1, p - v1)) > 0.0f &&
-        pt::dot(n, pt::cross(v0 - v2, p - v2)) > 0.0f)
-        return t;
-    return -1.0f;
-}
-
-float sphere_t(f3 o, f3 d) {   // :372-385
-    float t = INFINITY;
-    for (int si = 0; si < ns; si++) {
-        const float* s = &sph[8 * (size_t)si];
-        const f3 oc = o - ld3(s);
-        const float a = pt::dot(d, d), hb = pt::dot(oc, d), c = pt::dot(oc, oc) - s[3] * s[3];
-        const float disc = hb * hb - a * c;
-        const float ht = disc < 0.0f ? -1.0f : (-hb - std::sqrt(disc)) / a;
-        if (ht > 0.0001f && ht < t) t = ht;
-    }
-    return t;
-}
-
-// the leaf's 2-way choice (:411-428) at t; returns whether t moves
-bool leaf_choice(int bnode, f3 o, f3 d, float t, float& nt_, int& ntri) {
-    const float* b = &nodes[12 * (size_t)bnode];
-    const int t0 = (int)b[8], t1 = (int)b[9];
-    const float h1 = hit_triangle(o, d, t0), h2 = hit_triangle(o, d, t1);
-    if (h1 > 0.0001f && h1 < t && (h1 < h2 || h2 < 0.0001f)) { nt_ = h1; ntri = t0; return true; }
-    if (h2 > 0.0001f && h2 < t) { nt_ = h2; ntri = t1; return true; }
-    return false;
-}
-
-// the kernel's test of node i: its bounds near-first for the ray's direction signs (the octant
-// images of the LDS walk)
+// the kernel's tests of node i: its bounds near-first for the ray's direction signs (the octant
+// images of the LDS walk), with rd = pt::rcp_fast(d) as in the kernel's segment set-up
 struct CRay { f3 rd, ol, oh; bool sx, sy, sz; };
 CRay make_ray(f3 o, f3 d) {
     CRay r;
-    r.rd = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+    r.rd = mk(pt::rcp_fast(d.x), pt::rcp_fast(d.y), pt::rcp_fast(d.z));
     ptc::cull_addends(o, r.rd, cm, ws, r.ol, r.oh);
     r.sx = std::signbit(d.x); r.sy = std::signbit(d.y); r.sz = std::signbit(d.z);
     return r;
 }
-bool node_cull(int i, const CRay& r, float t, float c_lo) {
+void node_oct(int i, const CRay& r, ptp::Quad& A, ptp::Quad& B) {   // the node's record in the ray's octant image
     const float* b = &nodes[12 * (size_t)i];
-    return ptc::cull_hit(r.sx ? b[4] : b[0], r.sx ? b[0] : b[4], r.sy ? b[5] : b[1], r.sy ? b[1] : b[5],
-                         r.sz ? b[6] : b[2], r.sz ? b[2] : b[6], r.rd, r.ol, r.oh, t, c_lo);
+    A = {r.sx ? b[4] : b[0], r.sx ? b[0] : b[4], r.sy ? b[5] : b[1], r.sy ? b[1] : b[5]};
+    B = {r.sz ? b[6] : b[2], r.sz ? b[2] : b[6], 0.0f, 0.0f};
+}
+bool node_cull(int i, const CRay& r, float t, float c_lo) {
+    ptp::Quad A, B;
+    node_oct(i, r, A, B);
+    return pti::slab_oct_cons(A, B, r.rd, r.ol, r.oh, t, c_lo);
+}
+bool node_retest(int i, const CRay& r, f3 o, f3 d, float t) {   // the leaf phase's exact re-test
+    ptp::Quad A, B;
+    node_oct(i, r, A, B);
+    return pti::slab_oct(A, B, o, d, r.rd, t);
 }
 bool chain_cull(int i, const CRay& r, float t, float c_lo) {   // node i and every ancestor
     for (; i >= 0; i = parent[i])
@@ -115,49 +67,32 @@ bool chain_cull(int i, const CRay& r, float t, float c_lo) {   // node i and eve
     return true;
 }
 
-bool in_guard(f3 o, f3 d) {   // the exact-reciprocal guard, ray half
-    auto g0 = [](float v) { float a = std::fabs(v); return v == 0.0f || (a >= 0x1p-40f && a <= 0x1p60f); };
-    auto g1 = [](float v) { float a = std::fabs(v); return a >= 0x1p-20f && a <= 2.0f; };
-    return g0(o.x) && g0(o.y) && g0(o.z) && g1(d.x) && g1(d.y) && g1(d.z);
-}
-
 const float kNoWindow = -INFINITY;
 float c_lo_on = ptc::kWindowLo;
 long window_violations = 0, cons_violations = 0, mismatches = 0, slow = 0, near_hits = 0;
 struct Acc { double segs = 0, ref_nodes = 0, ref_leaves = 0, removed = 0, off_nodes = 0, off_leaves = 0, on_nodes = 0, on_leaves = 0; };
 
-struct Out { float t; int tri; long nodes, leaves; };
-// The reference walk; for guarded rays it also checks (b) / (c) at every node it visits and
-// counts the leaf visits the clause alone removes.
-Out ref_walk(f3 o, f3 d, float t0, bool guarded, const CRay& cr, Acc& A) {
-    Out r{t0, -1, 0, 0};
-    for (int bi = 0; bi > -1;) {
-        const float* b = &nodes[12 * (size_t)bi];
-        const bool hb = node_exact(bi, o, d, r.t);
-        r.nodes++;
-        if (guarded && hb && !node_cull(bi, cr, r.t, kNoWindow)) cons_violations++;
-        const int next = hb ? (int)b[10] : (int)b[11];
-        if (hb && b[8] > -1.0f) {
-            r.leaves++;
-            const bool kept = !guarded || chain_cull(bi, cr, r.t, c_lo_on);
-            if (guarded && !kept && chain_cull(bi, cr, r.t, kNoWindow)) A.removed++;
-            float t2;
-            int tri;
-            if (leaf_choice(bi, o, d, r.t, t2, tri)) {
-                if (!kept) {
-                    if (window_violations < 10)
-                        std::fprintf(stderr, "WINDOW o=(%a,%a,%a) d=(%a,%a,%a): leaf %d accepts t=%a, culled\n", o.x, o.y,
-                                     o.z, d.x, d.y, d.z, bi, t2);
-                    window_violations++;
-                }
-                if (t2 < 4e-4f) near_hits++;
-                r.t = t2;
-                r.tri = tri;
+typedef RefOut Out;
+// The reference walk (tests/ref_walk.h); for guarded rays it also checks (b) / (c) at every node it
+// visits and counts the leaf visits the clause alone removes.
+Out checked_ref_walk(f3 o, f3 d, float t0, bool guarded, const CRay& cr, Acc& A) {
+    return ref_walk(
+        o, d, t0,
+        [&](int bi, bool hb, float t) {
+            if (guarded && hb && !node_cull(bi, cr, t, kNoWindow)) cons_violations++;
+        },
+        [&](int bi, float t, bool moves, float t2) {
+            const bool kept = !guarded || chain_cull(bi, cr, t, c_lo_on);
+            if (guarded && !kept && chain_cull(bi, cr, t, kNoWindow)) A.removed++;
+            if (!moves) return;
+            if (!kept) {
+                if (window_violations < 10)
+                    std::fprintf(stderr, "WINDOW o=(%a,%a,%a) d=(%a,%a,%a): leaf %d accepts t=%a, culled\n", o.x, o.y,
+                                 o.z, d.x, d.y, d.z, bi, t2);
+                window_violations++;
             }
-        }
-        bi = next;
-    }
-    return r;
+            if (t2 < 4e-4f) near_hits++;
+        });
 }
 
 // The culling walk of the kernel: the conservative test at every node, and at a leaf the
@@ -174,7 +109,7 @@ Out cull_walk(f3 o, f3 d, float t0, const CRay& cr, float c_lo) {
             r.leaves++;
             float t2;
             int tri;
-            if (leaf_choice(bi, o, d, r.t, t2, tri) && node_exact(bi, o, d, r.t)) { r.t = t2; r.tri = tri; }
+            if (leaf_choice(bi, o, d, r.t, t2, tri) && node_retest(bi, cr, o, d, r.t)) { r.t = t2; r.tri = tri; }
         }
         bi = next;
     }
@@ -186,7 +121,7 @@ void segment(f3 o, f3 d, Acc& A, float* t_out, int* tri_out) {
     const bool guarded = in_guard(o, d);
     CRay cr{};
     if (guarded) cr = make_ray(o, d);
-    const Out ro = ref_walk(o, d, t0, guarded, cr, A);
+    const Out ro = checked_ref_walk(o, d, t0, guarded, cr, A);
     *t_out = ro.t;
     *tri_out = ro.tri;
     if (!guarded) { slow++; return; }
@@ -218,17 +153,7 @@ float ulps(float v, int k) {   // v moved k units in the last place (k < 0: towa
 
 int main(int argc, char** argv) {
     if (argc < 2) { std::fprintf(stderr, "usage: window_cull_sim scene.bin [stride] [bounces] [adversarial]\n"); return 2; }
-    FILE* f = std::fopen(argv[1], "rb");
-    if (!f) return 2;
-    int hdr[3];
-    if (std::fread(hdr, 4, 3, f) != 3) return 2;
-    nt = hdr[0]; nn = hdr[1]; ns = hdr[2];
-    if (nt < 1 || nn < 1) return 2;
-    tris.resize(16 * (size_t)nt); nodes.resize(12 * (size_t)nn); sph.resize(8 * (size_t)ns);
-    if (std::fread(tris.data(), 4, tris.size(), f) != tris.size() || std::fread(nodes.data(), 4, nodes.size(), f) != nodes.size() ||
-        std::fread(sph.data(), 4, sph.size(), f) != sph.size() || std::fread(cam, 4, 12, f) != 12)
-        return 2;
-    std::fclose(f);
+    if (!load_scene(argv[1]) || nt < 1 || nn < 1) return 2;
     const int stride = argc > 2 ? std::atoi(argv[2]) : 16;
     const int bounces = argc > 3 ? std::atoi(argv[3]) : 8;
     const long adversarial = argc > 4 ? std::atol(argv[4]) : 0;

@@ -1,0 +1,139 @@
+// TEST INFRASTRUCTURE: the reference side of the CPU walk models, once -- the scene file they read
+// and the reference's binary32 walk (calculateRayCollision, computeShader.c:367-432; bvh_intersect
+// :309-365; hit_triangle :274-307), restated on pt_math.h's pinned operations.  An independent
+// restatement: nothing here may call pt_isect.h, pt_cull.h or pt_wide.h, the kernel-side code
+// the models check against it.
+// Used by tests/wide/wide_sim.cpp, tests/wide/cert_fuzz.cpp and tests/cull/window_cull_sim.cpp.
+#pragma once
+
+#include "../opengl-path-tracing_amd/csrc/pt_math.h"
+
+#include <cmath>
+#include <cstdio>
+#include <utility>
+#include <vector>
+
+namespace ref {
+
+using pt::f3;
+using pt::mk;
+
+// scene.bin: int32 n_tris, n_nodes, n_spheres, then float32 tris (16 per), nodes (12 per),
+// spheres (8 per), camera (12: pos, dir, 0...) -- written by the tests that run the models
+inline std::vector<float> tris, nodes, sph;
+inline int nt = 0, nn = 0, ns = 0;
+inline float cam[12];
+inline bool load_scene(const char* path) {
+    FILE* f = std::fopen(path, "rb");
+    if (!f) return false;
+    int hdr[3];
+    bool ok = std::fread(hdr, 4, 3, f) == 3 && hdr[0] >= 0 && hdr[1] >= 0 && hdr[2] >= 0;
+    if (ok) {
+        nt = hdr[0]; nn = hdr[1]; ns = hdr[2];
+        tris.resize(16 * (size_t)nt); nodes.resize(12 * (size_t)nn); sph.resize(8 * (size_t)ns);
+        ok = std::fread(tris.data(), 4, tris.size(), f) == tris.size() &&
+             std::fread(nodes.data(), 4, nodes.size(), f) == nodes.size() &&
+             std::fread(sph.data(), 4, sph.size(), f) == sph.size() && std::fread(cam, 4, 12, f) == 12;
+    }
+    std::fclose(f);
+    return ok;
+}
+
+inline f3 ld3(const float* p) { return mk(p[0], p[1], p[2]); }
+
+// computeShader.c:309-365 in IEEE division (the reference's exact test)
+inline bool slab_exact(const float* lo, const float* hi, f3 o, f3 d, float cur_t) {
+    float tmin = (lo[0] - o.x) / d.x, tmax = (hi[0] - o.x) / d.x;
+    if (tmin > tmax) std::swap(tmin, tmax);
+    float tymin = (lo[1] - o.y) / d.y, tymax = (hi[1] - o.y) / d.y;
+    if (tymin > tymax) std::swap(tymin, tymax);
+    if ((tmin > tymax) || (tymin > tmax)) return false;
+    if (tymin > tmin) tmin = tymin;
+    if (tymax < tmax) tmax = tymax;
+    float tzmin = (lo[2] - o.z) / d.z, tzmax = (hi[2] - o.z) / d.z;
+    if (tzmin > tzmax) std::swap(tzmin, tzmax);
+    if ((tmin > tzmax) || (tzmin > tmax)) return false;
+    if (tzmin > tmin) tmin = tzmin;
+    return !(tmin > cur_t);
+}
+inline bool node_exact(int i, f3 o, f3 d, float t) {
+    const float* b = &nodes[12 * (size_t)i];
+    return slab_exact(b, b + 4, o, d, t);
+}
+
+// hit_triangle (:274-307): -1 on a miss; n out
+inline float hit_triangle(f3 o, f3 d, f3 v0, f3 v1, f3 v2, f3& n) {
+    n = pt::normalize(pt::cross(v1 - v0, v2 - v0));
+    const float dd = -pt::dot(n, v0);
+    const float t = -(pt::dot(n, o) + dd) / pt::dot(n, d);
+    if (t < 0.0f) return -1.0f;
+    const f3 p = o + d * t;
+    if (pt::dot(n, pt::cross(v1 - v0, p - v0)) > 0.0f && pt::dot(n, pt::cross(v2 - v1, p - v1)) > 0.0f &&
+        pt::dot(n, pt::cross(v0 - v2, p - v2)) > 0.0f)
+        return t;
+    return -1.0f;
+}
+inline float hit_triangle(f3 o, f3 d, int ti) {
+    const float* tr = &tris[16 * (size_t)ti];
+    f3 n;
+    return hit_triangle(o, d, ld3(tr), ld3(tr + 4), ld3(tr + 8), n);
+}
+
+inline float sphere_t(f3 o, f3 d) {   // :372-385 (the closest sphere hit in (1e-4, inf), else inf)
+    float t = INFINITY;
+    for (int si = 0; si < ns; si++) {
+        const float* s = &sph[8 * (size_t)si];
+        const f3 oc = o - ld3(s);
+        const float a = pt::dot(d, d), hb = pt::dot(oc, d), c = pt::dot(oc, oc) - s[3] * s[3];
+        const float disc = hb * hb - a * c;
+        const float ht = disc < 0.0f ? -1.0f : (-hb - std::sqrt(disc)) / a;
+        if (ht > 0.0001f && ht < t) t = ht;
+    }
+    return t;
+}
+
+// the leaf's 2-way choice (:411-428) at t; returns whether t moves
+inline bool leaf_choice(int bnode, f3 o, f3 d, float t, float& nt_, int& ntri) {
+    const float* b = &nodes[12 * (size_t)bnode];
+    const int t0 = (int)b[8], t1 = (int)b[9];
+    const float h1 = hit_triangle(o, d, t0), h2 = hit_triangle(o, d, t1);
+    if (h1 > 0.0001f && h1 < t && (h1 < h2 || h2 < 0.0001f)) { nt_ = h1; ntri = t0; return true; }
+    if (h2 > 0.0001f && h2 < t) { nt_ = h2; ntri = t1; return true; }
+    return false;
+}
+
+// The reference walk.  A model's own bookkeeping rides on two hooks: at_node(bi, hb, t) after
+// node bi's box test at t, and at_leaf(bi, t, moves, t2) at a leaf whose box was hit, after its
+// 2-way choice and before t moves to t2.
+struct RefOut { float t; int tri; long nodes, leaves; };
+template <class AtNode, class AtLeaf>
+RefOut ref_walk(f3 o, f3 d, float t0, AtNode at_node, AtLeaf at_leaf) {
+    RefOut r{t0, -1, 0, 0};
+    for (int bi = 0; bi > -1;) {
+        const float* b = &nodes[12 * (size_t)bi];
+        const bool hb = node_exact(bi, o, d, r.t);
+        r.nodes++;
+        at_node(bi, hb, r.t);
+        const int next = hb ? (int)b[10] : (int)b[11];
+        if (hb && b[8] > -1.0f) {
+            r.leaves++;
+            float t2 = 0.0f;
+            int tri = -1;
+            const bool moves = leaf_choice(bi, o, d, r.t, t2, tri);
+            at_leaf(bi, r.t, moves, t2);
+            if (moves) { r.t = t2; r.tri = tri; }
+        }
+        bi = next;
+    }
+    return r;
+}
+
+// The exact-reciprocal guard, ray half.  (A restatement: the kernel's own is an
+// expression inside k_render_sm's segment set-up, pt_render_sm.h, on pt::in_guard / in_range_abs.)
+inline bool in_guard(f3 o, f3 d) {
+    auto g0 = [](float v) { float a = std::fabs(v); return v == 0.0f || (a >= 0x1p-40f && a <= 0x1p60f); };
+    auto g1 = [](float v) { float a = std::fabs(v); return a >= 0x1p-20f && a <= 2.0f; };
+    return g0(o.x) && g0(o.y) && g0(o.z) && g1(d.x) && g1(d.y) && g1(d.z);
+}
+
+}  // namespace ref

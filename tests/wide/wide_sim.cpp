@@ -1,7 +1,8 @@
 // TEST INFRASTRUCTURE: CPU model of the wide global-memory walk (pt_wide.h) against the
 // reference's binary walk (calculateRayCollision, computeShader.c:367-432; bvh_intersect
-// :309-365; hit_triangle :274-307).  It runs the SAME per-lane functions the kernel runs
-// (ptw::wide_hits / wide_visit / wide_pop) on the host and, for every ray segment of a set of
+// :309-365; hit_triangle :274-307; tests/ref_walk.h).  It runs the SAME per-lane functions the
+// kernel runs (ptw::wide_hits / wide_visit / wide_pop, and pti::slab_fast with rd = pt::rcp_fast(d)
+// for the leaf re-test) on the host and, for every ray segment of a set of
 // diffuse paths and of adversarial rays, checks that
 //   (1) the wide walk ends with the reference walk's t (bitwise) and triangle,
 //   (2) every record child whose exact box test passes at the visit's t is accepted by the
@@ -12,8 +13,10 @@
 //   scene.bin: int32 n_tris, n_nodes, n_spheres, then float32 tris (16 per), nodes (12 per),
 //   spheres (8 per), camera (12: pos, dir, 0...) -- written by tests/test_wide_walk.py.
 // Exit status 0 = no mismatch.  Output: one JSON line of statistics.
+#include "../../opengl-path-tracing_amd/csrc/pt_isect.h"
 #include "../../opengl-path-tracing_amd/csrc/pt_scene_pack.h"
 #include "../../opengl-path-tracing_amd/csrc/pt_wide.h"
+#include "../ref_walk.h"
 
 #include <cmath>
 #include <cstdio>
@@ -23,112 +26,22 @@
 
 using pt::f3;
 using pt::mk;
+using namespace ref;   // the scene and the reference side
 
 namespace {
 
-std::vector<float> tris, nodes, sph;
-int nt = 0, nn = 0, ns = 0;
-float cam[12];
-
-// computeShader.c:309-365 in IEEE division (the reference's exact test)
-bool slab_exact(const float* lo, const float* hi, f3 o, f3 d, float cur_t) {
-    float tmin = (lo[0] - o.x) / d.x, tmax = (hi[0] - o.x) / d.x;
-    if (tmin > tmax) std::swap(tmin, tmax);
-    float tymin = (lo[1] - o.y) / d.y, tymax = (hi[1] - o.y) / d.y;
-    if (tymin > tymax) std::swap(tymin, tymax);
-    if ((tmin > tymax) || (tymin > tmax)) return false;
-    if (tymin > tmin) tmin = tymin;
-    if (tymax < tmax) tmax = tymax;
-    float tzmin = (lo[2] - o.z) / d.z, tzmax = (hi[2] - o.z) / d.z;
-    if (tzmin > tzmax) std::swap(tzmin, tzmax);
-    if ((tmin > tzmax) || (tzmin > tmax)) return false;
-    if (tzmin > tmin) tmin = tzmin;
-    return !(tmin > cur_t);
-}
-bool node_exact(int i, f3 o, f3 d, float t) {
-    const float* b = &nodes[12 * (size_t)i];
-    return slab_exact(b, b + 4, o, d, t);
-}
-
-f3 ld3(const float* p) { return mk(p[0], p[1], p[2]); }
-
-// :274-307
-float hit_triangle(f3 o, f3 d, int ti) {
-    const float* tr = &tris[16 * (size_t)ti];
-    const f3 v0 = ld3(tr), v1 = ld3(tr + 4), v2 = ld3(tr + 8);
-    const f3 n = pt::normalize(pt::cross(v1 - v0, v2 - v0));
-    const float dd = -pt::dot(n, v0);
-    const float t = -(pt::dot(n, o) + dd) / pt::dot(n, d);
-    if (t < 0.0f) return -1.0f;
-    const f3 p = o + d * t;
-    if (pt::dot(n, pt::cross(v1 - v0, p - v0)) > 0.0f && pt::dot(n, pt::cross(v2 - v1, p - v1)) > 0.0f &&
-        pt::dot(n, pt::cross(v0 - v2, p - v2)) > 0.0f)
-        return t;
-    return -1.0f;
-}
-
-float sphere_t(f3 o, f3 d) {   // :372-385 (the closest sphere hit in (1e-4, inf), else inf)
-    float t = INFINITY;
-    for (int si = 0; si < ns; si++) {
-        const float* s = &sph[8 * (size_t)si];
-        const f3 oc = o - ld3(s);
-        const float a = pt::dot(d, d), hb = pt::dot(oc, d), c = pt::dot(oc, oc) - s[3] * s[3];
-        const float disc = hb * hb - a * c;
-        const float ht = disc < 0.0f ? -1.0f : (-hb - std::sqrt(disc)) / a;
-        if (ht > 0.0001f && ht < t) t = ht;
-    }
-    return t;
-}
-
-struct Leaf { float t; int tri; };
-// the leaf's 2-way choice (:411-428) at t; returns whether t moves
-bool leaf_choice(int bnode, f3 o, f3 d, float t, float& nt_, int& ntri) {
-    const float* b = &nodes[12 * (size_t)bnode];
-    const int t0 = (int)b[8], t1 = (int)b[9];
-    const float h1 = hit_triangle(o, d, t0), h2 = hit_triangle(o, d, t1);
-    if (h1 > 0.0001f && h1 < t && (h1 < h2 || h2 < 0.0001f)) { nt_ = h1; ntri = t0; return true; }
-    if (h2 > 0.0001f && h2 < t) { nt_ = h2; ntri = t1; return true; }
-    return false;
-}
-
-struct RefOut { float t; int tri; long visits, leaves, top; };
 std::vector<unsigned char> ref_top_set;   // the binary walk's LDS top nodes (ptp::top_numbering)
-RefOut ref_walk(f3 o, f3 d, float t0) {
-    RefOut r{t0, -1, 0, 0, 0};
-    for (int bi = 0; bi > -1;) {
-        const float* b = &nodes[12 * (size_t)bi];
-        const bool hb = node_exact(bi, o, d, r.t);
-        r.visits++;
-        if (ref_top_set[bi]) r.top++;
-        const int next = hb ? (int)b[10] : (int)b[11];
-        if (hb && b[8] > -1.0f) {
-            r.leaves++;
-            float t2;
-            int tri;
-            if (leaf_choice(bi, o, d, r.t, t2, tri)) { r.t = t2; r.tri = tri; }
-        }
-        bi = next;
-    }
-    return r;
-}
 
 ptw::WideTree W;
 long cons_violations = 0;
 struct WideOut { float t; int tri; long visits, resumes, leaves, retests, retest_fail, pops, top_visits, lines, certified; };
 long cert_violations = 0;
 
-// the exact-reciprocal guard, ray half
-bool in_guard(f3 o, f3 d) {
-    auto g0 = [](float v) { float a = std::fabs(v); return v == 0.0f || (a >= 0x1p-40f && a <= 0x1p60f); };
-    auto g1 = [](float v) { float a = std::fabs(v); return a >= 0x1p-20f && a <= 2.0f; };
-    return g0(o.x) && g0(o.y) && g0(o.z) && g1(d.x) && g1(d.y) && g1(d.z);
-}
-
 int top_records = 512;   // indices below this are staged in LDS by the kernel
 
 WideOut wide_walk(f3 o, f3 d, float t0) {
     WideOut r{t0, -1, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const f3 rd = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+    const f3 rd = mk(pt::rcp_fast(d.x), pt::rcp_fast(d.y), pt::rcp_fast(d.z));
     const ptw::WRay wr = ptw::make_wray(o, rd, W.cw, std::signbit(d.x), std::signbit(d.y), std::signbit(d.z));
     int cur = 0, R = -1;
 #ifndef STACK_K
@@ -165,9 +78,9 @@ WideOut wide_walk(f3 o, f3 d, float t0) {
         int tri;
         if (leaf_choice(W.bn_of[g], o, d, r.t, t2, tri)) {
             r.retests++;
-            const float* lb = &W.lbox[(size_t)g * 8];
-            const float lo[3] = {lb[0], lb[2], lb[4]}, hi[3] = {lb[1], lb[3], lb[5]};
-            const bool exact = slab_exact(lo, hi, o, d, r.t);
+            const float* lb = &W.lbox[(size_t)g * 8];   // the kernel's re-test: slab_fast on wlbox[2g], [2g + 1]
+            const bool exact = pti::slab_fast(ptp::Quad{lb[0], lb[1], lb[2], lb[3]}, ptp::Quad{lb[4], lb[5], lb[6], lb[7]},
+                                              o, d, rd, r.t);
             const float* tr = &tris[16 * (size_t)tri];
             const f3 p = o + d * t2;
             const f3 v0 = ld3(tr), v1 = ld3(tr + 4), v2 = ld3(tr + 8);
@@ -190,13 +103,14 @@ struct Acc { double segs = 0, rv = 0, rl = 0, wv = 0, wr = 0, wl = 0, wt = 0, wf
 long mismatches = 0, slow = 0;
 void segment(f3 o, f3 d, Acc& A, float* t_out, int* tri_out) {
     const float t0 = sphere_t(o, d);
-    const RefOut ro = ref_walk(o, d, t0);
+    long top = 0;
+    const RefOut ro = ref_walk(o, d, t0, [&](int bi, bool, float) { top += ref_top_set[bi]; }, [](int, float, bool, float) {});
     *t_out = ro.t;
     *tri_out = ro.tri;
     A.segs++;
-    A.rv += ro.visits;
+    A.rv += ro.nodes;
     A.rl += ro.leaves;
-    A.ref_top += ro.top;
+    A.ref_top += top;
     if (!in_guard(o, d)) { slow++; return; }
     const WideOut wo = wide_walk(o, d, t0);
     uint32_t a, b;
@@ -222,16 +136,7 @@ void segment(f3 o, f3 d, Acc& A, float* t_out, int* tri_out) {
 
 int main(int argc, char** argv) {
     if (argc < 2) { std::fprintf(stderr, "usage: wide_sim scene.bin [stride] [bounces] [adversarial]\n"); return 2; }
-    FILE* f = std::fopen(argv[1], "rb");
-    if (!f) return 2;
-    int hdr[3];
-    if (std::fread(hdr, 4, 3, f) != 3) return 2;
-    nt = hdr[0]; nn = hdr[1]; ns = hdr[2];
-    tris.resize(16 * (size_t)nt); nodes.resize(12 * (size_t)nn); sph.resize(8 * (size_t)ns);
-    if (std::fread(tris.data(), 4, tris.size(), f) != tris.size() || std::fread(nodes.data(), 4, nodes.size(), f) != nodes.size() ||
-        std::fread(sph.data(), 4, sph.size(), f) != sph.size() || std::fread(cam, 4, 12, f) != 12)
-        return 2;
-    std::fclose(f);
+    if (!load_scene(argv[1])) return 2;
     const int stride = argc > 2 ? std::atoi(argv[2]) : 16;
     const int bounces = argc > 3 ? std::atoi(argv[3]) : 8;
     const long adversarial = argc > 4 ? std::atol(argv[4]) : 0;
