@@ -153,6 +153,10 @@ int pt_debug_launches(pt_ctx* ctx, unsigned long long out[2]);
  * slack (the largest of its three axes; 0 for a scene outside the conditions).  Either
  * pointer may be null. */
 int pt_debug_window_cull(pt_ctx* ctx, int* active, float* slack);
+/* The leaf sweep (tuning key 23): *swept = 1 when the render launch this context enqueued last
+ * ran it, *qualifies = 1 when the uploaded scene has a sweep table, *n_leaves = the scene's leaf
+ * pairs.  Any pointer may be null. */
+int pt_debug_sweep(pt_ctx* ctx, int* swept, int* qualifies, int* n_leaves);
 /* Sum of render-kernel durations (HIP events on the render stream) and the number of
  * launches since the last reset; reset != 0 clears both after reading. */
 int pt_timing(pt_ctx* ctx, double* total_kernel_ms, int* n_launches, int reset);
@@ -216,6 +220,9 @@ int pt_set_kernel(pt_ctx* ctx, int variant);
  * key 22 = window clause of the LDS culling walk (0 = automatic, 1 = off).  The walk skips a
  *         box that ends before the distance window (1e-4, t) in which a triangle can be
  *         accepted; off, launches run the generic kernel without the clause.
+ * key 23 = leaf sweep (0 = automatic, 1 = off: the culling walk).  In a scene of a few leaves
+ *         a ray inside the exact-reciprocal guard tests every leaf box once per segment, with
+ *         bounds that are the same for all lanes, instead of walking the tree ("The leaf sweep").
  * None of these change the image (each pixel's frames stay in order in one lane). */
 int pt_set_tuning(pt_ctx* ctx, int key, int value);
 

@@ -1,6 +1,7 @@
 // pt_cull.h -- the node test of the LDS culling walk, shared by the HIP kernel
 // (pt_render.hip), the scene packer (pt_scene_pack.h: the scene's window slack) and the CPU walk model
-// (tests/cull/window_cull_sim.cpp).
+// (tests/cull/window_cull_sim.cpp); and, at the end of the file, the same test in the form the leaf sweep of
+// tiny scenes runs it (sweep_mask; CPU model tests/cull/leaf_sweep_sim.cpp).
 //
 // The test is conservative on two sides.  Inside the exact-reciprocal guard every quotient is
 // finite and normal or zero.  With u = 2^-24, q = RN(RN(b - o) / d) the reference's quotient and
@@ -185,6 +186,91 @@ inline bool window_slack(const float* bvh, int n_nodes, const float* tris, float
         if (!(worst[q] < 0x1p60)) return false;
     for (int q = 0; q < 3; q++) ws[q] = nextafterf((float)(1.25 * worst[q] * (1.0 + 0x1p-20)), inf);
     return true;
+}
+
+// ------------------------------------------------------------------ the leaf sweep ("The leaf sweep")
+// A scene of a few leaves (ptl::kSweepMaxLeaves at most) does not walk: at segment set-up a ray inside the guard tests
+// every leaf's own box once, at the segment's initial t0, and keeps the passing leaves as a bit mask in chain order
+// (bit k = the k-th leaf the reference walk can reach); the leaf phase then visits the set bits from the lowest up
+// and re-tests each leaf's box exactly at the current t before a triangle may move t, as it does for the culling
+// walk.  The (t, triangle) of every segment are the reference's:
+//   (a) the reference reaches a leaf only if the exact test of the leaf and of every ancestor passes at the t
+//       current at that moment;
+//   (b) t never grows and the exact test is monotone in t (tn <= min(tf, t)), so a leaf that passes at its visit
+//       time passes at t0;
+//   (c) the sweep's test is cull_hit's (below), which accepts whatever the exact test accepts at that t (1), and
+//       with the window clause rejects only a leaf none of whose triangles can be accepted (the lemma): the mask
+//       holds every leaf at which the reference moves t;
+//   (d) in a nested tree a leaf's box lies inside every ancestor's, so its exact pass at t implies theirs at t and,
+//       by (b), at the larger t of their own visits: the exact re-test of the leaf's box at the current t says
+//       whether the reference visits the leaf, and t is the reference's by induction over the visits;
+//   (e) the bits are taken in chain order, so equal distances resolve as in the reference.
+// The rays of a wave differ in their octant, so the near-first images are of no use here.  Instead the ray's
+// reciprocal is split by sign, rp_i = rd_i where rd_i > 0 else 0 and rn_i = rd_i - rp_i, and
+//   near_i = fma(lo_i, rp_i, fma(hi_i, rn_i, ol_i)),   far_i = fma(hi_i, rp_i, fma(lo_i, rn_i, oh_i)).
+// One of rp_i, rn_i is zero and the bounds are finite (the scene half of the guard), so the inner fma returns its
+// addend exactly and the outer one is cull_hit's fma on the octant image, bit for bit -- up to the sign of a zero,
+// which only enters comparisons.  The proof above therefore holds as it stands.  The bounds are the same for every
+// lane: the kernel reads them through a wave-uniform index, as scalar operands.
+struct SweepRay { pt::f3 rp, rn, ol, oh; };
+PT_HD SweepRay sweep_ray(pt::f3 rd, pt::f3 ol, pt::f3 oh) {
+    SweepRay r;
+    r.rp = pt::mk(rd.x > 0.0f ? rd.x : 0.0f, rd.y > 0.0f ? rd.y : 0.0f, rd.z > 0.0f ? rd.z : 0.0f);
+    r.rn = pt::mk(rd.x > 0.0f ? 0.0f : rd.x, rd.y > 0.0f ? 0.0f : rd.y, rd.z > 0.0f ? 0.0f : rd.z);
+    r.ol = ol;
+    r.oh = oh;
+    return r;
+}
+// One box in the reference order (lo, hi per axis) at t0.
+PT_HD bool sweep_hit(float lx, float hx, float ly, float hy, float lz, float hz, const SweepRay& r, float t0, float c_lo) {
+    const float xn = __builtin_fmaf(lx, r.rp.x, __builtin_fmaf(hx, r.rn.x, r.ol.x));
+    const float xf = __builtin_fmaf(hx, r.rp.x, __builtin_fmaf(lx, r.rn.x, r.oh.x));
+    const float yn = __builtin_fmaf(ly, r.rp.y, __builtin_fmaf(hy, r.rn.y, r.ol.y));
+    const float yf = __builtin_fmaf(hy, r.rp.y, __builtin_fmaf(ly, r.rn.y, r.oh.y));
+    const float zn = __builtin_fmaf(lz, r.rp.z, __builtin_fmaf(hz, r.rn.z, r.ol.z));
+    const float zf = __builtin_fmaf(hz, r.rp.z, __builtin_fmaf(lz, r.rn.z, r.oh.z));
+    const float tn = fmaxf(fmaxf(xn, yn), zn);
+    const float tf = fminf(fminf(xf, yf), zf);
+    return fmaxf(tn, c_lo) <= min_t(tf, t0);
+}
+// mask + mask + hit: the box's verdict enters as the carry of one add
+PT_HD unsigned sweep_push(unsigned m, bool hit) {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(PT_SWEEP_NO_ADDC)
+    // (the compiler makes a select and a shift-or of the C++ form, two instructions: +1.0% on C2 for this one)
+    unsigned r;
+    const unsigned long long c = __builtin_amdgcn_ballot_w64(hit);   // the compare's own lane mask
+    unsigned long long co;
+    asm("v_addc_co_u32 %0, %1, %2, %2, %3" : "=v"(r), "=s"(co) : "v"(m), "s"(c));
+    return r;
+#else
+    return m + m + (hit ? 1u : 0u);
+#endif
+}
+// The candidate mask of a ray inside the guard: bit k is set when the box of sweep-table entry k passes at t0.
+// table: 2 quads per entry, {lo.x, hi.x, lo.y, hi.y}, {lo.z, hi.z, pair, 0} (ptp::kSweep), indexable by int; n <= 32.
+// The boxes run from the last to the first so that a set bit enters as the carry of mask + mask.
+// (Requesting box k - 1's bounds before box k's test measured 0.5% slower on C2 than this plain loop: the other
+// resident waves already cover the scalar loads' latency.)
+template <class T>
+PT_HD unsigned sweep_mask(const SweepRay& r, float t0, float c_lo, T table, int n) {
+    unsigned m = 0u;
+    for (int k = n - 1; k >= 0; k--) {
+        const auto a = table[2 * k], b = table[2 * k + 1];
+        m = sweep_push(m, sweep_hit(a.x, a.y, a.z, a.w, b.x, b.y, r, t0, c_lo));
+    }
+    return m;
+}
+template <class T>
+PT_HD unsigned sweep_mask(pt::f3 rd, pt::f3 ol, pt::f3 oh, float t0, float c_lo, T table, int n) {
+    return sweep_mask(sweep_ray(rd, ol, oh), t0, c_lo, table, n);
+}
+// The sweep's first test where the camera stands outside the scene (KParams::sweep_root): the root box, by the same
+// test.  Every leaf box lies inside it (a nested tree), the reference reaches a leaf only past the root's exact test
+// at some t <= t0, which this test then passes too, and the lemma's (e) gives the root's far planes the window
+// clause's bound wherever a leaf's triangle is accepted: a ray that fails here has no leaf to visit.  A wave none of
+// whose rays passes skips the sweep, as the walk ends at its first node.
+PT_HD bool sweep_root_hit(const float box[6], const SweepRay& r, float t0, float c_lo) {
+    return sweep_hit(box[0], box[1], box[2], box[3], box[4], box[5], r, t0, c_lo);
 }
 
 }  // namespace ptc

@@ -28,7 +28,7 @@
 
 // internal hooks of pt_render.hip (not part of the public ABI): kSceneBufs device scene
 // buffers of a context (ptp::SceneBuf), and the flag that lets a replicated context render
-constexpr int kSceneBufs = ptp::kBufs;
+constexpr int kSceneBufs = ptp::kBufsAll;
 extern "C" int pt__scene_replicate_layout(pt_ctx* dst, const pt_ctx* src, void* dptr[kSceneBufs],
                                           const void* sptr[kSceneBufs], size_t bytes[kSceneBufs]);
 extern "C" int pt__scene_set_ready(pt_ctx* c, int ready);

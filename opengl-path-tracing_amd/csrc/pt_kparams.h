@@ -69,6 +69,10 @@ struct KParams {
     float wide_cw[3];              // ... 2^-18 * the scene's largest |coordinate| per axis, rounded up (WRay)
     int leaf_cert;                 // culling / wide walk: skip the exact leaf re-test where the hit certifies it
     float2* moments;               // k_accum_frames<.., true>: luminance moments (S1, S2) beside accum (pt_noise.h)
+    const float4* sweep_tab;       // the leaf sweep's table (ptp::kSweep), 2 quads per leaf in chain order
+    int n_sweep;                   // ... its leaves (<= ptl::kSweepMaxLeaves)
+    int sweep;                     // LDS scene, 256 threads: guarded rays sweep the leaf boxes instead of walking
+    int sweep_root;                // ... after the root box's own test (the camera stands outside the root box)
 };
 
 struct Cnt {

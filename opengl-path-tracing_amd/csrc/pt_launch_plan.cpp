@@ -42,6 +42,12 @@ bool window_cull_on(const SceneFacts& f, const Tuning& t, int flags, bool counti
     return cons_walk_on(f, t, counting) && !t.win_off && !f.win_bad && !(flags & PT_FLAG_MOLLER_TRUMBORE);
 }
 
+// Whether the guarded rays of an LDS launch sweep the leaf boxes instead of walking ("The leaf sweep"): the launch
+// would run the culling walk, the scene has a sweep table, and key 23 leaves it on.
+bool sweep_on(const SceneFacts& f, const Tuning& t, bool counting) {
+    return cons_walk_on(f, t, counting) && f.sweep_ok && !t.sweep_off;
+}
+
 // Whether a global-memory launch walks the wide tree: the scene has one (a nested tree), it lies
 // inside the scene half of the exact-reciprocal guard (otherwise no lane could use it), tuning key 16 leaves it on,
 // nothing is counted (counting builds keep the binary walk: their counts are the reference's), and the occupancy is
@@ -188,6 +194,7 @@ LaunchPlan plan_launch(const SceneFacts& f, const Tuning& t, const Image& im, co
     // re-test (-1.9%, same-process A/B r05c)
     p.leaf_cert = f.leaf_cert_ok && !t.cert_off && !(im.flags & PT_FLAG_MOLLER_TRUMBORE) && p.wide;
     p.leaf_thresh = t.leaf_thresh ? t.leaf_thresh : (lds_scene ? 52 : 20);
+    // (a sweeping launch has its own, kSweepShadeThresh: set below, once the workgroup is known)
     p.shade_thresh = t.shade_thresh ? t.shade_thresh : (lds_scene ? 44 : 24);
     // walk floor: 5 for the small LDS scenes (C2), 8 for the wide-workgroup ones (keysweep on the 150 / 380-triangle
     // stand-ins: +0.8% / +1.2% over 5), 6 for global memory
@@ -275,6 +282,9 @@ LaunchPlan plan_launch(const SceneFacts& f, const Tuning& t, const Image& im, co
     p.dyn_lds_bytes = p.lds ? lds : (p.wide ? (size_t)p.wide_top * 48 : (size_t)p.n_top * 32) + shade_lds_bytes;
     p.key = kernel_key(s.counting, p.lds, p.wide, p.split, p.mw, im.rpp, p.nt, f.walk_np);
     p.common = common_launch(f, t, im, p);
+    // the sweep is in the 256-thread LDS lines only (a scene with a sweep table is far below the wide workgroups' sizes)
+    p.sweep = p.lds && p.nt == 256 && sweep_on(f, t, s.counting);
+    if (p.sweep && !t.shade_thresh) p.shade_thresh = kSweepShadeThresh;
     if (p.split) {  // the accumulate pass: the long variant loads 8 frames per group
         p.accum_long = n_frames > kShortLaunch;
         p.accum_moments = s.moments;

@@ -38,6 +38,25 @@ constexpr int kMaxSlots = 4, kAutoSlots = 3;
 #define PT_ACCUM_PIX 4
 #endif
 constexpr int kAccumPix = PT_ACCUM_PIX, kAccumPixLong = 2;
+// The leaf sweep ("The leaf sweep"): scenes of at most this many leaves test every leaf box once per segment instead
+// of walking the tree.  A lane's candidate leaves are one 32-bit mask, so 32 is the ceiling.  24 by the A/B on seeded
+// soups and quad rows of 5 to 32 leaves (HISTORY.md, round 12; profiles/ab/r12_leaf_sweep/cap_ab.txt): +1.5 to +4.7% at 5, 8,
+// 11, 16, 21, 24 and 25 leaves against the culling walk, and from about 30 leaves the sink image costs a resident
+// workgroup, so such scenes run neither.  The sweep costs 18 vector instructions per leaf and segment whatever the
+// ray: it loses where the walk ends after two or three nodes (-28% on a 27-leaf soup seen across a large floor), and
+// the cap bounds that loss.  PT_SWEEP_MAX_LEAVES overrides it for A/B builds.
+#ifndef PT_SWEEP_MAX_LEAVES
+#define PT_SWEEP_MAX_LEAVES 24
+#endif
+constexpr int kSweepMaxLeaves = PT_SWEEP_MAX_LEAVES;
+static_assert(kSweepMaxLeaves >= 1 && kSweepMaxLeaves <= 32, "a lane's candidate set is one 32-bit mask");
+// The shade threshold of a sweeping launch.  Without a walk phase the wave runs the leaf phase whenever fewer lanes
+// than this wait to shade, so the threshold alone sets the lane use of both phases: swept on C2's generic line
+// (256-frame launches, ms) 24: 110.1, 32: 106.8, 40: 98.2, 44: 94.7, 48: 93.3, 56: 92.8, 62: 99.9.
+#ifndef PT_SWEEP_SHADE_THRESH
+#define PT_SWEEP_SHADE_THRESH 56
+#endif
+constexpr int kSweepShadeThresh = PT_SWEEP_SHADE_THRESH;
 
 // What ptp::pack_scene (pt_scene_pack.h) learns about a scene (pt_ctx holds one by value).
 struct SceneFacts {
@@ -55,6 +74,10 @@ struct SceneFacts {
     float win_slack[3] = {0, 0, 0}; // KParams::win_slack (ptc::window_slack)
     bool win_bad = false;           // the scene is outside the window clause's conditions (pt_cull.h): no clause
     float wide_cw[3] = {0, 0, 0};
+    int n_leaves = 0;               // leaf pairs (n_slots / 2)
+    // the scene has a sweep table (ptp::kSweep): a nested tree inside the scene half of the exact-reciprocal guard and
+    // the window clause's conditions, of at most kSweepMaxLeaves leaves whose pair indices follow the chain order
+    bool sweep_ok = false;
 };
 
 // The pt_set_tuning values and the kernel variant (pt_ctx holds one by value).
@@ -79,6 +102,7 @@ struct Tuning {
     bool adaptive = true;           // key 2: adaptive tile order
     int common_off = 0;             // key 21: 1 = never the specialised default-path kernel (LaunchPlan::common)
     int win_off = 0;                // key 22: 1 = the culling walk without its window clause (pt_cull.h)
+    int sweep_off = 0;              // key 23: 1 = no leaf sweep (the culling walk instead)
 };
 
 // the context's share of the image and its device; what else a launch depends on
@@ -108,6 +132,9 @@ struct LaunchPlan {
     // holds the default configuration's launch-uniform facts as constants (common_launch).  Beside the key, not in
     // it: the launch still has its generic line, which enqueue_render takes when a fact only it can see fails.
     bool common;
+    // Guarded rays sweep the scene's leaf boxes instead of walking (pt_cull.h, sweep_mask).  The COMMON line is built
+    // with it on and with it off; a generic LDS line reads it as a kernel argument.
+    bool sweep;
 };
 
 // The template arguments of the one line built with COMMON (the default path of a Cornell-sized scene).
@@ -116,6 +143,7 @@ constexpr KernelKey kCommonKey = {false, true, 7, false, true, true, 256, false}
 // Whether the LDS walk culls (also pt_stats_ex[15]), and the bound on a launch's queue ids.
 bool cons_walk_on(const SceneFacts& f, const Tuning& t, bool counting);
 bool window_cull_on(const SceneFacts& f, const Tuning& t, int flags, bool counting);
+bool sweep_on(const SceneFacts& f, const Tuning& t, bool counting);
 unsigned long long id_limit(const Tuning& t, const Image& im);
 
 // Everything a launch of n_frames decides before it touches HIP.  `graph`: the launch is captured

@@ -75,7 +75,7 @@ struct pt_ctx {
     int n_launches = 0;
     float4* accum = nullptr;
     uchar4* rgba8 = nullptr;
-    float4* d_scene[ptp::kBufs] = {};   // the device scene (ptp::SceneBuf); null: the scene has no such buffer
+    float4* d_scene[ptp::kBufsAll] = {};   // the device scene (ptp::SceneBuf); null: the scene has no such buffer
     ptl::SceneFacts sf;             // what ptp::pack_scene learned (the launch planner's input)
     ptl::Tuning tun;                // pt_set_tuning values and the kernel variant
     unsigned long long* d_counters = nullptr;
@@ -121,6 +121,7 @@ struct pt_ctx {
     unsigned long long last_counts[16] = {0};
     unsigned long long n_line_launches[2] = {0, 0};   // render launches enqueued on a generic / a COMMON line (pt_debug_launches)
     bool count_pending = false;
+    bool last_swept = false;        // the last render launch enqueued ran the leaf sweep (pt_debug_sweep)
     // asynchronous presentation (pt_present_begin / _end): per buffer a pinned host image and
     // its copy event; the device view is rgba8 (one, as the copies and the passes that write
     // it are ordered on the context stream)
@@ -192,6 +193,7 @@ static void free_scene(pt_ctx* c) {
     }
     c->sf.wide_ok = false;
     c->sf.n_wide = 0;
+    c->sf.sweep_ok = false;
     c->scene_ok = false;
 }
 
@@ -301,7 +303,7 @@ int pt_upload_scene(pt_ctx* c, const float* tris, int n_tris, const float* bvh, 
     HIPCHK(c, hipStreamSynchronize(c->stream));   // a render in flight may still read the old scene
     drop_graph(c);
     free_scene(c);
-    for (int b = 0; b < ptp::kBufs; b++) {
+    for (int b = 0; b < ptp::kBufsAll; b++) {
         const size_t bytes = packed.buf[b].size() * sizeof(float);
         if (!bytes) continue;
         HIPCHK(c, hipMalloc(&c->d_scene[b], bytes));
@@ -386,6 +388,7 @@ static const TuningKey kTuningKeys[] = {
     {19, &ptl::Tuning::cert_off, in_0_1, "leaf re-test certificate: 0 = automatic, 1 = off", true},
     {21, &ptl::Tuning::common_off, in_0_1, "specialised default-path kernel: 0 = automatic, 1 = off", true},
     {22, &ptl::Tuning::win_off, in_0_1, "window clause of the culling walk: 0 = automatic, 1 = off", true},
+    {23, &ptl::Tuning::sweep_off, in_0_1, "leaf sweep: 0 = automatic, 1 = off", true},
 };
 
 int pt_set_tuning(pt_ctx* c, int key, int value) {
@@ -534,9 +537,13 @@ static const RenderKernel kRenderKernels[] = {PT_RENDER_KERNELS(PT_X)};
 #define PT_X(C, L, MW, M, S, P, NT, W) {{C, L, MW, M, S, P, NT, W}, k_render_sm<C, L, MW, M, S, P, NT, W, true>},
 static const RenderKernel kRenderKernelsCommon[] = {PT_RENDER_KERNELS_COMMON(PT_X)};
 #undef PT_X
-static const RenderKernel* find_kernel(const ptl::KernelKey& key, bool common = false) {
+// ... and those once more with the leaf sweep as a constant too (the plan's `sweep`)
+#define PT_X(C, L, MW, M, S, P, NT, W) {{C, L, MW, M, S, P, NT, W}, k_render_sm<C, L, MW, M, S, P, NT, W, true, true>},
+static const RenderKernel kRenderKernelsCommonSweep[] = {PT_RENDER_KERNELS_COMMON(PT_X)};
+#undef PT_X
+static const RenderKernel* find_kernel(const ptl::KernelKey& key, bool common = false, bool sweep = false) {
     if (common) {
-        for (const RenderKernel& k : kRenderKernelsCommon)
+        for (const RenderKernel& k : sweep ? kRenderKernelsCommonSweep : kRenderKernelsCommon)
             if (k.key == key) return &k;
         return nullptr;
     }
@@ -598,6 +605,12 @@ static KParams fill_params(const pt_ctx* c, const ptl::LaunchPlan& pl, int frame
     // the plan
     p.n_top = pl.n_top, p.wide_top = pl.wide_top, p.shade_lds = pl.shade_lds;
     p.cons_walk = pl.cons_walk, p.leaf_cert = pl.leaf_cert;
+    p.sweep = pl.sweep, p.sweep_tab = d[ptp::kSweep], p.n_sweep = c->sf.sweep_ok ? c->sf.n_leaves : 0;
+    {   // a camera outside the root box: its rays take the root's test before the sweep (pt_cull.h, sweep_root_hit)
+        const float* rb = c->sf.root_box;
+        p.sweep_root = !(c->cam[0] >= rb[0] && c->cam[0] <= rb[1] && c->cam[1] >= rb[2] && c->cam[1] <= rb[3] &&
+                         c->cam[2] >= rb[4] && c->cam[2] <= rb[5]);
+    }
     p.leaf_thresh = pl.leaf_thresh, p.shade_thresh = pl.shade_thresh, p.trav_floor = pl.trav_floor;
     p.compact_max = c->tun.compact_max;
     p.group = pl.group, p.pull_batch = pl.pull_batch, p.grp_magic = pl.grp_magic;
@@ -641,7 +654,11 @@ static int enqueue_render(pt_ctx* c, int frame_first, int n_frames, int acc_firs
     }
     if (c->rows_local == 0) return PT_OK;
     const bool common = pl.common && common_params_ok(c, p, n_frames);
-    const RenderKernel* kernel = find_kernel(pl.key, common);
+    // a sweeping launch has its table: the plan's `sweep` needs sweep_ok, and a scene with sweep_ok was packed with one
+    if (pl.sweep && (!p.sweep_tab || p.n_sweep < 1 || p.n_sweep > ptl::kSweepMaxLeaves || 2 * p.n_sweep != p.n_slots))
+        return fail(c, PT_E_STATE, "internal: a sweeping launch without a sweep table");
+    const RenderKernel* kernel = find_kernel(pl.key, common, pl.sweep);
+    c->last_swept = pl.sweep;
     if (!kernel) {
         const ptl::KernelKey& k = pl.key;
         char key[96];
@@ -897,15 +914,15 @@ int pt_get_config(const pt_ctx* c, pt_config* out) {
 // buffers of the same sizes, contents undefined -- and returns both contexts' buffer pointers
 // and sizes, so the caller can fill dst's from src's (an RCCL broadcast across devices or a
 // device copy).  Both contexts must have the same width (tile facts are per image).
-int pt__scene_replicate_layout(pt_ctx* dst, const pt_ctx* src, void* dptr[ptp::kBufs], const void* sptr[ptp::kBufs],
-                               size_t bytes[ptp::kBufs]) {
+int pt__scene_replicate_layout(pt_ctx* dst, const pt_ctx* src, void* dptr[ptp::kBufsAll], const void* sptr[ptp::kBufsAll],
+                               size_t bytes[ptp::kBufsAll]) {
     if (!dst || !src || !dptr || !sptr || !bytes) return PT_E_ARG;
     if (!src->scene_ok) return fail(dst, PT_E_STATE, "source context has no scene");
     HIPCHK(dst, hipSetDevice(dst->cfg.device));
     HIPCHK(dst, hipStreamSynchronize(dst->stream));
     drop_graph(dst);
     free_scene(dst);
-    for (int i = 0; i < ptp::kBufs; i++) {
+    for (int i = 0; i < ptp::kBufsAll; i++) {
         bytes[i] = ptp::buf_quads(src->sf, i) * sizeof(float4);
         sptr[i] = src->d_scene[i];
         if (bytes[i]) HIPCHK(dst, hipMalloc(&dst->d_scene[i], bytes[i]));
@@ -1199,6 +1216,14 @@ int pt_debug_window_cull(pt_ctx* c, int* active, float* slack) {
     if (!c) return PT_E_ARG;
     if (active) *active = ptl::window_cull_on(c->sf, c->tun, c->cfg.flags, c->counting) ? 1 : 0;
     if (slack) *slack = std::max(c->sf.win_slack[0], std::max(c->sf.win_slack[1], c->sf.win_slack[2]));
+    return PT_OK;
+}
+
+int pt_debug_sweep(pt_ctx* c, int* swept, int* qualifies, int* n_leaves) {
+    if (!c) return PT_E_ARG;
+    if (swept) *swept = c->last_swept ? 1 : 0;
+    if (qualifies) *qualifies = c->sf.sweep_ok ? 1 : 0;
+    if (n_leaves) *n_leaves = c->sf.n_leaves;
     return PT_OK;
 }
 

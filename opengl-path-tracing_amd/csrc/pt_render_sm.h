@@ -77,6 +77,9 @@ extern __shared__ float4 g_lds[];   // the state-machine kernel's scene copy (no
 // (scenes of at most kPadNodes nodes: images padded to that count, pt_launch_plan.h)
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) const v4f lds_v4f;
+// launch-constant data read through a wave-uniform index (the leaf sweep's table): in the constant address space
+// such reads are scalar loads, and the values arrive as scalar operands
+typedef __attribute__((address_space(4))) const v4f const_v4f;
 template <bool LDS, bool PADN = false>
 __device__ __forceinline__ void node_at(const SceneView& S, int i, float4& lo, float4& hi) {
     if (LDS) {      // i = byte offset from the LDS base, which is 0 (checked at kernel entry)
@@ -247,6 +250,9 @@ __device__ __forceinline__ void leaf_pair_tests(const SceneView& S, bool at, int
 //   TRAV  otherwise (an inner walk loop that yields when either threshold is reached).
 // A lane's own operation sequence is exactly the reference's (node, leaf tests before the
 // next node, same t), so results are bit-identical; only lane interleaving changes.
+// With the leaf sweep (scenes of a few leaves, pt_cull.h) a ray inside the guard never enters
+// TRAV: its segment set-up leaves the candidate leaves as a bit mask in bi, and the lane stays
+// in LEAF until the mask is empty.
 // =====================================================================================
 enum : int { ST_DONE = 0, ST_TRAV = 1, ST_LEAF = 2, ST_SHADE = 3 };
 #ifndef PT_WALK_UNROLL
@@ -481,9 +487,12 @@ __device__ unsigned long long g_wave_trace[kWaveTraceMax * 4];
 // (DESIGN.md §5.2): mode, flags and the culling walk give about 1.8% each, the tile facts 0.3%,
 // the single sphere nothing in time (7 fewer spilled SGPRs); the thresholds and the walk floor
 // are not here because as constants they cost 1.1%.
-template <bool COMMON>
+// The leaf sweep (pt_cull.h, DESIGN.md §5.6, "The leaf sweep") is such a fact too: the COMMON line is built with it on and with it
+// off (SWEEP), so tuning key 23 compares the two walks of one kernel; a generic line reads the kernel argument.
+template <bool COMMON, bool SWEEP = false>
 struct LaunchFacts {
     const KParams& p;
+    __device__ __forceinline__ bool sweep() const { return COMMON ? SWEEP : p.sweep != 0; }
     __device__ __forceinline__ int mode() const { return COMMON ? 1 : p.mode; }
     __device__ __forceinline__ int flags() const { return COMMON ? 0 : p.flags; }
     __device__ __forceinline__ bool cons_walk() const { return COMMON || p.cons_walk != 0; }
@@ -498,11 +507,19 @@ struct LaunchFacts {
 };
 
 template <bool COUNT, bool LDS, int MINW, bool MULTI, bool SPLIT, bool PADN = false, int NT = 256, bool WIDE = false,
-          bool COMMON = false>
+          bool COMMON = false, bool SWEEP = false>
 __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
     static_assert(!WIDE || (!LDS && !COUNT), "the wide walk is the global-memory walk of a render build");
     static_assert(!COMMON || (!COUNT && LDS && !MULTI && SPLIT && PADN), "COMMON is the default path's LDS line");
-    const LaunchFacts<COMMON> F{p};
+    static_assert(!SWEEP || COMMON, "SWEEP is a constant of the COMMON line; generic lines read KParams::sweep");
+    const LaunchFacts<COMMON, SWEEP> F{p};
+    // the leaf sweep: 256-thread LDS render lines only (wave-uniform; with it on the walk culls, ptl::sweep_on)
+#ifdef PT_DIAG_TRIS_GLOBAL
+    const bool sweep = false;   // (the diagnostic build reads the triangles in the upload's order)
+#else
+    const bool sweep = LDS && !COUNT && !WIDE && NT == 256 && F.sweep();
+#endif
+    const const_v4f* const sweep_tab = (const const_v4f*)(size_t)p.sweep_tab;
 #ifdef PT_WAVE_TRACE
     const unsigned long long wt_entry = __builtin_amdgcn_s_memrealtime();
     unsigned wt_items = 0;
@@ -520,7 +537,17 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
         const float4* wsrc = sk ? p.sc.walk_sk : p.sc.walk_lds;
         const int nm = 3 * p.n_mats, ns = 2 * F.n_spheres();
         for (int i = threadIdx.x; i < nn; i += blockDim.x) lds[i] = wsrc[i];   // ready-made image
-        for (int i = threadIdx.x; i < nt; i += blockDim.x) lds[nn + (i & 3) * T + (i >> 2)] = p.sc.tris[i];
+        if (sweep) {
+            // the leaf sweep numbers the leaves by their chain position (a candidate bit is one), so this copy holds
+            // leaf pair q's two slots at 2 c, 2 c + 1, c = the chain position of pair q (the table's inverse map):
+            // every slot index the kernel keeps (s0, hprim) then is one of this copy
+            for (int i = threadIdx.x; i < nt; i += blockDim.x) {
+                const int slot = i >> 2, c = __float_as_int(p.sweep_tab[2 * (slot >> 1) + 1].w);
+                lds[nn + (i & 3) * T + 2 * c + (slot & 1)] = p.sc.tris[i];
+            }
+        } else {
+            for (int i = threadIdx.x; i < nt; i += blockDim.x) lds[nn + (i & 3) * T + (i >> 2)] = p.sc.tris[i];
+        }
         for (int i = threadIdx.x; i < nm; i += blockDim.x) lds[nn + nt + i] = p.sc.mats[i];
         for (int i = threadIdx.x; i < ns; i += blockDim.x) lds[nn + nt + nm + i] = p.sc.spheres[i];
         __syncthreads();
@@ -883,10 +910,30 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
                     wR = -1;
                 }
                 st = walk ? ST_TRAV : ST_SHADE;
+                if (sweep) {
+                    // the leaf sweep: a ray inside the guard tests every leaf box once at this t and never walks;
+                    // bi carries its candidate leaves, lowest bit first (the root-inside test, the octant image and
+                    // the walk start above are only for the rays outside the guard, which walk from the root)
+                    unsigned cand = 0u;
+                    if (walk & fast_seg) {
+                        f3 ol, oh;
+                        ptc::cull_addends(o, rd, S.cm, S.ws, ol, oh);
+                        const ptc::SweepRay sr = ptc::sweep_ray(rd, ol, oh);
+                        // a camera outside the root box (wave-uniform): many of its rays miss the scene, and a wave
+                        // of them skips the sweep on the root's own test
+                        bool in = true;
+                        if (p.sweep_root) in = ptc::sweep_root_hit(p.root_box, sr, t, S.clo);
+                        if (in) cand = ptc::sweep_mask(sr, t, S.clo, sweep_tab, p.n_sweep);
+                    }
+                    bi = walk ? (fast_seg ? (int)cand : 0) : -1;
+                    st = walk ? (fast_seg ? (cand ? ST_LEAF : ST_SHADE) : ST_TRAV) : ST_SHADE;
+                }
             }
         } else if (nL > 0 && (nL >= p.leaf_thresh || low)) {
             // ---------------- LEAF: both triangle tests + the 2-way choice (:406-429)
             const bool at = st == ST_LEAF;
+            // the leaf sweep: a lane inside the guard holds its candidate leaves in bi and visits the lowest
+            const bool swept = sweep & fast;
             int s0 = 0, cont = -1;
             bool cop = false;
             float4 nd0 = make_float4(0, 0, 0, 0);
@@ -901,12 +948,19 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
                     cop = (gc & 1) != 0;
                 }
                 if (LDS && !COUNT && F.cons_walk()) {   // sinks carry the pair k only
-                    s0 = 2 * leaf;
+                    int lp = leaf;
+                    // a sweeping launch holds the slots in chain order: a candidate bit is a chain position (a swept
+                    // lane at a leaf has a bit set); a ray outside the guard walked to pair `leaf`
+                    // (entry 0 for a swept lane, whose `leaf` is stale: the read stays inside the table)
+                    if (sweep) lp = swept ? __ffs(bi) - 1 : __float_as_int(p.sweep_tab[2 * (swept ? 0 : leaf) + 1].w);
+                    s0 = 2 * lp;
                     cop = __float_as_int(tri_quad<LDS>(S, s0 + 1, 1).w) != 0;
                 }
                 nd0 = tri_quad<LDS>(S, s0, 0);               // {n, d0} of the first triangle
-                cont = LDS ? __float_as_int(tri_quad<LDS>(S, s0, 1).w) : bi;   // LDS: next-right, image 0
-                if (LDS && (fast & (cont >= 0))) cont += oct_base(d, S.np << 5);
+                if (!swept) {
+                    cont = LDS ? __float_as_int(tri_quad<LDS>(S, s0, 1).w) : bi;   // LDS: next-right, image 0
+                    if (LDS && (fast & (cont >= 0))) cont += oct_base(d, S.np << 5);
+                }
             }
             float h1 = -1.0f, h2 = -1.0f;
             bool ca = false, cb = false;   // the chosen triangle certifies its leaf's box (pt_wide.h)
@@ -958,6 +1012,9 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
                 if (WIDE && fast) {   // the next pending child, or the resume position
                     bi = ptw::wide_pop<kWideStack>(we, wR);
                     st = bi >= 0 ? ST_TRAV : (bi == -1 ? ST_SHADE : ST_LEAF);
+                } else if (swept) {   // the next candidate, or the segment is finished
+                    bi &= bi - 1;
+                    st = bi ? ST_LEAF : ST_SHADE;
                 } else {
                     bi = cont;
                     st = bi > -1 ? ST_TRAV : ST_SHADE;
@@ -971,7 +1028,8 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
             const unsigned long long live = LDS ? mS | mL | mT : __ballot(st != ST_DONE);
             const bool all_fast = LDS ? (__ballot(fast) & mT) == mT : __all(fast || st != ST_TRAV);
             if (LDS && !COUNT && F.cons_walk()) {    // the culling walk (kernel argument: uniform)
-                if (all_fast)
+                // (with the leaf sweep only rays outside the guard walk, on the exact test)
+                if (all_fast && !sweep)
                     trav_walk<true, COUNT, LDS, PADN, true>(S, o, d, rd, fast, t, live, mT, mL, mS, p.leaf_thresh, p.shade_thresh, p.trav_floor, st, bi, leaf, c);
                 else
                     trav_walk<false, COUNT, LDS, PADN, true>(S, o, d, rd, fast, t, live, mT, mL, mS, p.leaf_thresh, p.shade_thresh, p.trav_floor, st, bi, leaf, c);

@@ -123,6 +123,7 @@ size_t buf_quads(const ptl::SceneFacts& f, int b) {
     case kWideLeafBox: return 2 * ni;
     case kWideNodes: return ni ? buf_quads(f, kNodes) : 0;
     case kWideTris: return 8 * ni;
+    case kSweep: return f.sweep_ok ? 2 * (size_t)f.n_leaves : 0;
     default: return 0;
     }
 }
@@ -315,7 +316,37 @@ int pack_scene(const float* tris, int n_tris, const float* bvh, int n_nodes, con
         const int a = as_int(r1.z);
         sf.root_child = a >= 0 ? a : -1;
     }
-    for (int b = 0; b < kBufs; b++)
+    // The leaf sweep's table (pt_cull.h, sweep_mask; DESIGN.md §5.6, "The leaf sweep"): the leaves in chain order -- an internal node
+    // leads to its hit link, a leaf to its miss link, which in a nested tree passes every node in preorder -- each
+    // with its own box in the reference order and its triangle-pair index, and beside them the inverse map (entry p's
+    // last word: the chain position of pair p).  A lane's candidates are the bits of one word, bit k = chain position
+    // k, so the scene qualifies only when it has at most kSweepMaxLeaves leaves and the chain reaches all of them.  Its
+    // test is the culling walk's with the window clause, on exact quotients: the nested tree, the clause's conditions
+    // and the scene half of the guard as there.
+    sf.n_leaves = n_leaves;
+    sf.sweep_ok = false;
+    if (nested && !sf.win_bad && sf.scene_fast && n_leaves >= 1 && n_leaves <= ptl::kSweepMaxLeaves) {
+        std::vector<int> chain;
+        for (int i = 0; i >= 0 && (int)chain.size() <= n_leaves;) {
+            const float* nd = bvh + 12 * (size_t)i;
+            if (leaf_slot[i] >= 0) chain.push_back(i);
+            i = (int)nd[leaf_slot[i] >= 0 ? 11 : 10];
+        }
+        if ((int)chain.size() == n_leaves) {   // (an orphan leaf, which no walk reaches, has no position)
+            Quad* const dsw = quads(kSweep, 2 * (size_t)n_leaves);
+            for (int k = 0; k < n_leaves; k++) {
+                const float* nd = bvh + 12 * (size_t)chain[k];
+                const int pair = leaf_slot[chain[k]];
+                dsw[2 * k] = {nd[0], nd[4], nd[1], nd[5]};
+                dsw[2 * k + 1].x = nd[2];
+                dsw[2 * k + 1].y = nd[6];
+                dsw[2 * k + 1].z = as_float(pair);
+                dsw[2 * pair + 1].w = as_float(k);
+            }
+            sf.sweep_ok = true;
+        }
+    }
+    for (int b = 0; b < kBufsAll; b++)
         if (out.buf[b].size() != 4 * buf_quads(sf, b))
             return fail(err, PT_E_SCENE, "internal: scene buffer " + std::to_string(b) + " has not the size of its facts");
     return PT_OK;

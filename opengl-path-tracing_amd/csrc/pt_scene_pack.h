@@ -28,7 +28,12 @@ enum SceneBuf {
     kWideLeafBox,  // its exact leaf boxes, 2 quads per index
     kWideNodes,    // kNodes with leaf codes numbered by the wide index
     kWideTris,     // kTris numbered by the wide index
-    kBufs
+    kBufs,         // the buffers above: the rows of tests/golden/scene_packs.txt list exactly these
+    // the leaf sweep's table (pt_cull.h, sweep_mask): per leaf in chain order -- the order the reference walk reaches
+    // them -- 2 quads, {lo.x, hi.x, lo.y, hi.y}, {lo.z, hi.z, its pair index, the chain position of pair k (the
+    // inverse map)}; only for a scene with sweep_ok.  A sweeping kernel stages the triangle slots in chain order.
+    kSweep = kBufs,
+    kBufsAll       // every device buffer of a scene
 };
 
 // global-memory scenes: the first kTopNodes device nodes (breadth-first from the root) are
@@ -44,7 +49,7 @@ struct Quad { float x, y, z, w; };
 static_assert(sizeof(Quad) == 16, "a device quad");
 
 struct PackedScene {
-    std::vector<float> buf[kBufs];   // 4 floats per quad
+    std::vector<float> buf[kBufsAll];   // 4 floats per quad
     ptl::SceneFacts facts;
 };
 

@@ -127,6 +127,7 @@ def lib():
             "pt_stats_ex": (ip, [vp, np.ctypeslib.ndpointer(np.uint64)]),
             "pt_debug_launches": (ip, [vp, np.ctypeslib.ndpointer(np.uint64)]),
             "pt_debug_window_cull": (ip, [vp, C.POINTER(ip), C.POINTER(fp)]),
+            "pt_debug_sweep": (ip, [vp, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]),
             "pt_set_tuning": (ip, [vp, ip, ip]),
             "pt_progressive_setup": (ip, [vp, ip, ip]),
             "pt_progressive_reset": (ip, [vp, ip]),
@@ -396,6 +397,20 @@ class PathTracer:
         self._check(lib().pt_debug_window_cull(self.h, C.byref(a), C.byref(s)))
         return bool(a.value), float(s.value)
 
+    def set_sweep(self, enable):
+        """Tuning key 23: the leaf sweep of scenes with a few leaves (on by default where the scene
+        qualifies; DESIGN.md §5.6, "The leaf sweep").  Never changes the image."""
+        self._check(lib().pt_set_tuning(self.h, 23, 0 if enable else 1))
+
+    def leaf_sweep(self):
+        """pt_debug_sweep -> dict(swept: the last launch ran the sweep, qualifies: the scene has a
+        sweep table, n_leaves: its leaf pairs)."""
+        a, q, n = C.c_int(), C.c_int(), C.c_int()
+        fn = getattr(lib(), "pt_debug_sweep", None)     # (an older build loaded with PT_LIB_PARTIAL has none)
+        if fn is not None:
+            self._check(fn(self.h, C.byref(a), C.byref(q), C.byref(n)))
+        return dict(swept=bool(a.value), qualifies=bool(q.value), n_leaves=int(n.value))
+
     def launches(self):
         """pt_debug_launches -> (launches on a generic line, on the specialised line)."""
         v = np.zeros(2, np.uint64)
@@ -496,7 +511,8 @@ class PathTracer:
         util = lambda w, l: float(v[l]) / max(1.0, 64.0 * float(v[w]))
         return dict(trav_iters=int(v[5]), trav_util=util(5, 6), leaf_iters=int(v[7]), leaf_util=util(7, 8),
                     seg_iters=int(v[9]), seg_util=util(9, 10), slow_segments=int(v[11]), nan_segments=int(v[12]),
-                    lds_bytes=int(v[13]), lds_bytes_sinks=int(v[14]), culling_walk=bool(v[15]))
+                    lds_bytes=int(v[13]), lds_bytes_sinks=int(v[14]), culling_walk=bool(v[15]),
+                    swept=self.leaf_sweep()["swept"])
 
     def copy_rows_device(self, dst_ptr, nbytes):
         self._check(lib().pt_copy_rows_device(self.h, C.c_void_p(dst_ptr), nbytes))
