@@ -157,6 +157,14 @@ int pt_debug_window_cull(pt_ctx* ctx, int* active, float* slack);
  * ran it, *qualifies = 1 when the uploaded scene has a sweep table, *n_leaves = the scene's leaf
  * pairs.  Any pointer may be null. */
 int pt_debug_sweep(pt_ctx* ctx, int* swept, int* qualifies, int* n_leaves);
+/* The adaptive tile order (tuning key 2), read only: waits for the context's work, then
+ * *sorts = the tile-order sorts run since the last scene upload (a captured graph's sorts count
+ * once per replay), *n_tiles and *tiles_x = the work queue's tile grid (tuning key 20), and
+ * perm_out[0 .. *n_tiles) = the order the next launch reads, one (ty << 16) | tx per tile
+ * (PT_E_ARG when max_tiles is smaller than the grid).  Any pointer may be null.  Changes no
+ * launch. */
+int pt_debug_tile_order(pt_ctx* ctx, unsigned long long* sorts, unsigned* perm_out, int max_tiles, int* n_tiles,
+                        int* tiles_x);
 /* Sum of render-kernel durations (HIP events on the render stream) and the number of
  * launches since the last reset; reset != 0 clears both after reading. */
 int pt_timing(pt_ctx* ctx, double* total_kernel_ms, int* n_launches, int reset);

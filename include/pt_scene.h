@@ -72,7 +72,11 @@ int pt_bvh_build(const float* tris, int n_tris, float* nodes_out, int max_nodes,
 /* The same builder on GPU `device`: one tree level at a time, the
  * chained stable centroid sorts as segmented device sorts, the prefix / suffix candidate
  * boxes as segmented scans, the split choice one thread per node.  Output identical to
- * pt_bvh_build (same node numbering, bounds, leaf indices and links).  Needs a GPU. */
+ * pt_bvh_build (same node numbering, bounds, leaf indices and links).  Needs a GPU.
+ * Both builders: PT_E_ARG for a null `tris` or `n_nodes` or n_tris <= 0 ("empty triangle list"),
+ * PT_E_SCENE above 2^23 triangles (checked before any data is read) and for non-finite data,
+ * PT_E_ARG with *n_nodes set when max_nodes is too small; a null nodes_out returns the count
+ * only.  The GPU builder returns the argument errors before any device call. */
 int pt_bvh_build_gpu(const float* tris, int n_tris, float* nodes_out, int max_nodes, int* n_nodes,
                      int device);
 /* pt_scene_build_bvh with the GPU builder. */

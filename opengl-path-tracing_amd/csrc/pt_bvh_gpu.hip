@@ -238,6 +238,7 @@ thread_local std::string g_err;   // this builder's message, handed to pt_bvh_la
         hipError_t e_ = (call);                                         \
         if (e_ != hipSuccess) {                                         \
             g_err = std::string(#call) + ": " + hipGetErrorString(e_);  \
+            (void)hipGetLastError(); /* not left for the next build */  \
             return PT_E_HIP;                                            \
         }                                                               \
     } while (0)
@@ -245,6 +246,9 @@ thread_local std::string g_err;   // this builder's message, handed to pt_bvh_la
 inline unsigned blocks_for(long long n) { return (unsigned)((n + 255) / 256); }
 
 int build(const float* T, int n, int device, std::vector<DNode>& nodes) {
+    // hipcub reads the thread's sticky last error after its launches: one left behind by an earlier
+    // failed call on this thread (a build on a device that does not exist) would fail this build
+    (void)hipGetLastError();
     int prev_device = 0;
     GCHK(hipGetDevice(&prev_device));
     struct DeviceGuard { int d; ~DeviceGuard() { (void)hipSetDevice(d); } } dg{prev_device};   // the caller's device back

@@ -93,6 +93,9 @@ struct pt_ctx {
     unsigned persist_blocks = 2048;
     int order_skip = 0;             // short launches since the last tile-order sort
     bool order_sorted = false;      // a sort ran since the scene upload
+    // k_tile_order launches since the scene upload (pt_debug_tile_order): enqueued directly, and
+    // per replay of the captured graph
+    unsigned long long n_sorts = 0, graph_sorts = 0;
     int n_cu = 0;
     float* d_rgb = nullptr;        // per-(frame, pixel) colours of the frame-split mode
     size_t rgb_bytes = 0;
@@ -312,6 +315,7 @@ int pt_upload_scene(pt_ctx* c, const float* tris, int n_tris, const float* bvh, 
     c->sf = packed.facts;
     c->order_sorted = false;      // the next sort pools the new scene's first short launches
     c->order_skip = 0;
+    c->n_sorts = 0;
     c->scene_ok = true;
     return PT_OK;
 }
@@ -700,6 +704,7 @@ static int enqueue_render(pt_ctx* c, int frame_first, int n_frames, int acc_firs
          ++c->order_skip >= (c->order_sorted ? kOrderEvery : kOrderFirst))) {
         c->order_skip = 0;
         c->order_sorted = true;
+        c->n_sorts++;
         hipLaunchKernelGGL(k_tile_order, dim3(1), dim3(1024), 0, c->stream, c->d_tile_cost, c->d_tile_perm,
                            c->n_tiles, c->tiles_x);
         if (!frame_dev) {   // later overlapped renders start after the new order
@@ -817,6 +822,7 @@ int pt_progressive_setup(pt_ctx* c, int frames_per_launch, int launches_per_repl
         if (rc0) return rc0;
     }
     HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+    const unsigned long long sorts_before = c->n_sorts;   // captured sorts run (and count) per replay
     int rc = PT_OK;
     for (int i = 0; i < launches_per_replay && rc == PT_OK; i++)
         rc = enqueue_frames(c, 0, frames_per_launch, 0, c->d_frame, i * frames_per_launch);
@@ -826,6 +832,8 @@ int pt_progressive_setup(pt_ctx* c, int frames_per_launch, int launches_per_repl
     }
     hipGraph_t g = nullptr;
     hipError_t e = hipStreamEndCapture(c->stream, &g);
+    c->graph_sorts = c->n_sorts - sorts_before;
+    c->n_sorts = sorts_before;
     if (rc != PT_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
     if (e != hipSuccess) return fail(c, PT_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
     c->graph = g;
@@ -860,7 +868,10 @@ int pt_progressive_run(pt_ctx* c, int replays) {
         if (rc) return rc;
     }
     HIPCHK(c, hipEventRecord(ev[0], c->stream));
-    for (int r = 0; r < replays; r++) HIPCHK(c, hipGraphLaunch(c->graph_exec, c->stream));
+    for (int r = 0; r < replays; r++) {
+        HIPCHK(c, hipGraphLaunch(c->graph_exec, c->stream));
+        c->n_sorts += c->graph_sorts;
+    }
     if (c->moments) c->mom_frames += replays * c->graph_frames;
     HIPCHK(c, hipEventRecord(c->ev_fence, c->stream));   // the replays sort the tile order
     c->fence_rec = true;
@@ -931,6 +942,7 @@ int pt__scene_replicate_layout(pt_ctx* dst, const pt_ctx* src, void* dptr[ptp::k
     dst->sf = src->sf;
     dst->order_sorted = false;
     dst->order_skip = 0;
+    dst->n_sorts = 0;
     // scene_ok stays false until the caller has filled the buffers (pt__scene_set_ready): a
     // failed broadcast or copy must not leave a context rendering from uninitialised memory
     dst->scene_ok = false;
@@ -1231,6 +1243,21 @@ int pt_debug_launches(pt_ctx* c, unsigned long long out[2]) {
     if (!c || !out) return PT_E_ARG;
     out[0] = c->n_line_launches[0];
     out[1] = c->n_line_launches[1];
+    return PT_OK;
+}
+
+int pt_debug_tile_order(pt_ctx* c, unsigned long long* sorts, unsigned* perm_out, int max_tiles, int* n_tiles,
+                        int* tiles_x) {
+    if (!c) return PT_E_ARG;
+    if (perm_out && max_tiles < c->n_tiles) return fail(c, PT_E_ARG, "tile order buffer too small");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    // the sorts run on the context stream, which waits for every render before them
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (sorts) *sorts = c->n_sorts;
+    if (n_tiles) *n_tiles = c->n_tiles;
+    if (tiles_x) *tiles_x = c->tiles_x;
+    if (perm_out && c->n_tiles > 0)
+        HIPCHK(c, hipMemcpy(perm_out, c->d_tile_perm, (size_t)c->n_tiles * sizeof(unsigned), hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

@@ -128,6 +128,7 @@ def lib():
             "pt_debug_launches": (ip, [vp, np.ctypeslib.ndpointer(np.uint64)]),
             "pt_debug_window_cull": (ip, [vp, C.POINTER(ip), C.POINTER(fp)]),
             "pt_debug_sweep": (ip, [vp, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]),
+            "pt_debug_tile_order": (ip, [vp, C.POINTER(C.c_ulonglong), vp, ip, C.POINTER(ip), C.POINTER(ip)]),
             "pt_set_tuning": (ip, [vp, ip, ip]),
             "pt_progressive_setup": (ip, [vp, ip, ip]),
             "pt_progressive_reset": (ip, [vp, ip]),
@@ -268,14 +269,22 @@ class SceneBuffers(dict):
     """The five SSBO contents of setupBuffers(): tris, nodes, mats, spheres, cam."""
 
 
-def setupBuffers(obj_path, mtl_path, camera=None):
-    """ogl_path_trace.h:367-530: load, build the BVH, append built-ins + metal sphere."""
+def setupBuffers(obj_path, mtl_path, camera=None, device=None, robust=False):
+    """ogl_path_trace.h:367-530: load, build the BVH, append built-ins + metal sphere.
+    device: None = the host builder, else pt_scene_build_bvh_gpu on that device (the same nodes).
+    robust: read the OBJ with the general Wavefront reader (pt_scene_load_obj_ex, PT_LOAD_ROBUST)."""
     h = C.c_void_p()
-    rc = lib().pt_scene_load_obj(str(obj_path).encode(), str(mtl_path).encode(), C.byref(h))
+    if robust:
+        rc = lib().pt_scene_load_obj_ex(str(obj_path).encode(), None if mtl_path is None else str(mtl_path).encode(),
+                                        1, C.byref(h))
+        if not h.value:
+            raise PTError(rc, "pt_scene_load_obj_ex failed")
+    else:
+        rc = lib().pt_scene_load_obj(str(obj_path).encode(), str(mtl_path).encode(), C.byref(h))
     s = _Scene(h)
     s.check(rc)
     s.check(lib().pt_scene_add_builtins(s.h))
-    s.check(lib().pt_scene_build_bvh(s.h))
+    s.check(lib().pt_scene_build_bvh(s.h) if device is None else lib().pt_scene_build_bvh_gpu(s.h, int(device)))
     a = s.arrays()
     a["cam"] = DEFAULT_CAMERA.copy() if camera is None else np.asarray(camera, np.float32).reshape(12)
     return SceneBuffers(a)
@@ -410,6 +419,19 @@ class PathTracer:
         if fn is not None:
             self._check(fn(self.h, C.byref(a), C.byref(q), C.byref(n)))
         return dict(swept=bool(a.value), qualifies=bool(q.value), n_leaves=int(n.value))
+
+    def tile_order(self):
+        """pt_debug_tile_order -> dict(sorts: tile-order sorts since the scene upload, n_tiles, tiles_x:
+        the tile grid, perm: the order the next launch reads as (n_tiles, 2) int (ty, tx)).  Waits
+        for the context's work."""
+        n, tx, sorts = C.c_int(), C.c_int(), C.c_ulonglong()
+        self._check(lib().pt_debug_tile_order(self.h, None, None, 0, C.byref(n), None))
+        perm = np.zeros(max(n.value, 1), np.uint32)
+        self._check(lib().pt_debug_tile_order(self.h, C.byref(sorts), perm.ctypes.data, len(perm), C.byref(n),
+                                              C.byref(tx)))
+        perm = perm[: n.value]
+        return dict(sorts=int(sorts.value), n_tiles=n.value, tiles_x=tx.value,
+                    perm=np.stack([perm >> 16, perm & 0xffff], 1).astype(np.int64))
 
     def launches(self):
         """pt_debug_launches -> (launches on a generic line, on the specialised line)."""

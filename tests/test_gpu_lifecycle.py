@@ -320,8 +320,11 @@ def test_read_rgba8_fused_view(cornell_scene):
 def test_tile_shapes_bitwise(cornell_scene, world):
     """Tuning key 20: the work queue's 64-pixel tiles as 8x8, 16x4, 32x2 or 64x1 (local rows of
     a row-split rank).  The tile shape changes only which lanes render which pixels together:
-    every shape, switched between renders of one context (with a learned tile order, a captured
-    graph and overlapped short launches), gives the oracle's image for every rank."""
+    every shape, switched between renders of one context (with a captured graph and overlapped
+    short launches), gives the oracle's image for every rank.  No launch here reads a learned tile
+    order: every set_key(20, ...) that changes the shape resets the order, and three short launches
+    stay below the first sort.  tests/test_gpu_tile_order.py learns an order for every shape and
+    checks it."""
     W, Hh = 100, 44                       # partial tiles on both edges for every shape
     want = O.render(cornell_scene, W, Hh, max_bounce=6, n_frames=5)
     for rank in range(world):
