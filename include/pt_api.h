@@ -283,6 +283,49 @@ int pt_noise_host(const float* moments, const unsigned char* in_footprint, size_
 int pt_render_until(pt_ctx* ctx, int frame_first, int accumulate_first, int batch, int max_frames,
                     float target, int* frames_done, pt_noise_stats* last);
 
+/* Adaptive sampling: pt_render_until's batches, but every tile of the work
+ * queue stops on its own.  The unit is the queue's tile, (8 << s) columns x (8 >> s) local rows
+ * (tuning key 20), numbered ty * tiles_x + tx as in pt_debug_tile_order; a row-split context
+ * decides on its own local tiles.  Frames frame_first, frame_first + 1, ... are rendered `batch`
+ * at a time (the last batch may be shorter) for the tiles still active, and for no other tile.
+ * After a batch, with n = n0 + the frames done so far (n0 = 0 for a restarting call, the
+ * context's frame count for accumulate_first = 1), an active tile retires when the sum of q =
+ * quantise(S1, S2, n) over its footprint pixels is at most (unsigned)(target * 65536.0f) times
+ * their number.  A retired tile is frozen: the call neither reads nor writes its image pixels
+ * and moments again, so a pixel holds the image and the moments of pt_render(frame_first, f,
+ * accumulate_first), bit for bit, f being the frames its tile received.  A tile without a
+ * footprint pixel (outside PT_FLAG_REF_DISPATCH's footprint, beyond the local rows) is never
+ * active and has f = 0.  The call ends when no tile is active or after max_frames frames;
+ * *frames_done = the frames the longest-lived tile received in this call.  Turns the moments on
+ * if they are off.  Synchronous: one host round trip per batch.
+ *
+ * Afterwards the moments hold per-tile frame counts: pt_read_moments reports the largest, and
+ * pt_noise, pt_render_until, pt_group_noise and a further pt_render_adaptive with
+ * accumulate_first = 1 return PT_E_STATE until a restarting render (accumulate = 0) or
+ * pt_set_moments makes the counts uniform again.  Plain renders are allowed at any time and
+ * behave as ever.  The contexts of a pt_group are not coordinated: group support is out of
+ * scope, each context of a group would stop its tiles alone.
+ * PT_E_ARG: batch < 2, max_frames < batch or target <= 0.  PT_E_STATE: before an upload. */
+typedef struct {
+    pt_noise_stats noise;              /* every footprint pixel quantised with its own tile's n;
+                                          frames = the largest n */
+    unsigned long long tiles;          /* tiles that hold a footprint pixel */
+    unsigned long long tiles_active;   /* ... of them, still above the target at the stop */
+    unsigned long long pixel_frames;   /* sum over tiles of footprint pixels x f */
+} pt_adaptive_stats;
+int pt_render_adaptive(pt_ctx* ctx, int frame_first, int accumulate_first, int batch, int max_frames,
+                       float target, int* frames_done, pt_adaptive_stats* last);
+/* The frames f each tile received in the last pt_render_adaptive: waits for the context's work,
+ * then *n_tiles and *tiles_x = the tile grid and dst[0 .. *n_tiles) = f per tile (PT_E_ARG when
+ * max_tiles is smaller than the grid; all 0 before the first adaptive call).  Any pointer may
+ * be null. */
+int pt_read_tile_frames(pt_ctx* ctx, unsigned* dst, int max_tiles, int* n_tiles, int* tiles_x);
+/* The stop rule on the host, of one tile's n_pixels moment pairs (in_footprint as in
+ * pt_noise_host): *retires = 1 when the tile would retire after `frames` frames.  No device is
+ * touched: the rule is the device kernel's own code.  PT_E_ARG as pt_noise_host. */
+int pt_tile_retires_host(const float* moments, const unsigned char* in_footprint, size_t n_pixels, int frames,
+                         float target, int* retires);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,8 +52,13 @@ static void usage() {
                  "                  mean luminance over the mean, pt_api.h: pt_render_until) is at most X,\n"
                  "                  checked every --batch B frames (default 16), at most --max-spp N frames\n"
                  "                  (default --spp); one GPU, not with --resume or --events\n"
+                 "  --adaptive      with --noise-target: every work-queue tile stops on its own once its mean\n"
+                 "                  relative error meets the target (pt_api.h: pt_render_adaptive)\n"
+                 "  --spp-map F     with --adaptive: the frames each tile received as a binary PGM, one pixel\n"
+                 "                  per tile, top row first (16-bit when a count exceeds 255)\n"
                  "  --json          print a JSON summary line (with --noise-target also frames_done,\n"
-                 "                  noise_mean, noise_max, noise_above_frac)\n"
+                 "                  noise_mean, noise_max, noise_above_frac; with --adaptive also tiles,\n"
+                 "                  tiles_active, pixel_frames)\n"
                  "  --gpu-bvh       build the BVH on GPU 0 (pt_bvh_build_gpu; the same nodes)\n");
 }
 
@@ -180,7 +185,9 @@ int main(int argc, char** argv) {
     std::string checkpoint, resume;
     float noise_target = 0.0f;            // > 0: render until converged (pt_render_until)
     int batch = 16, max_spp = 0;
-    bool until = false;
+    bool until = false, adaptive = false;
+    std::string spp_map;
+    pt_adaptive_stats astats = {{0, 0, 0, 0, 0}, 0, 0, 0};
     for (int i = 3; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&](void) -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
@@ -200,6 +207,8 @@ int main(int argc, char** argv) {
         else if (a == "--checkpoint") checkpoint = next();
         else if (a == "--resume") resume = next();
         else if (a == "--noise-target") { noise_target = (float)std::atof(next()); until = true; }
+        else if (a == "--adaptive") adaptive = true;
+        else if (a == "--spp-map") spp_map = next();
         else if (a == "--batch") batch = std::atoi(next());
         else if (a == "--max-spp") max_spp = std::atoi(next());
         else if (a == "--json") json = true;
@@ -210,6 +219,14 @@ int main(int argc, char** argv) {
     if (spp < 1 || chunk < 1 || gpus < 1 || ranks < 1) { usage(); return 2; }
     if (events && (!resume.empty() || !checkpoint.empty())) {
         std::fprintf(stderr, "--events excludes --resume / --checkpoint\n");
+        return 2;
+    }
+    if (adaptive && !until) {
+        std::fprintf(stderr, "--adaptive needs --noise-target\n");
+        return 2;
+    }
+    if (!spp_map.empty() && !adaptive) {
+        std::fprintf(stderr, "--spp-map needs --adaptive\n");
         return 2;
     }
     if (until) {
@@ -320,7 +337,31 @@ int main(int argc, char** argv) {
     } else if (until) {
         // frames 1.. in batches until the noise summary meets the target (or max_spp frames)
         int done = 0;
-        CHECK(pt_render_until(ctx[0], 1, 0, batch, max_spp, noise_target, &done, &noise), ctx[0]);
+        if (adaptive) {     // ... each tile until it meets the target on its own
+            CHECK(pt_render_adaptive(ctx[0], 1, 0, batch, max_spp, noise_target, &done, &astats), ctx[0]);
+            noise = astats.noise;
+            if (!spp_map.empty()) {
+                int nt = 0, tx = 1;
+                CHECK(pt_read_tile_frames(ctx[0], nullptr, 0, &nt, &tx), ctx[0]);
+                std::vector<unsigned> fr((size_t)std::max(nt, 1), 0u);
+                CHECK(pt_read_tile_frames(ctx[0], fr.data(), nt, &nt, &tx), ctx[0]);
+                unsigned mx = 0;
+                for (int t = 0; t < nt; t++) mx = std::max(mx, fr[t]);
+                const int ty = tx > 0 ? nt / tx : 0, maxval = mx > 255 ? 65535 : 255;
+                FILE* f = std::fopen(spp_map.c_str(), "wb");
+                if (!f) { std::fprintf(stderr, "cannot write %s\n", spp_map.c_str()); return 1; }
+                std::fprintf(f, "P5\n%d %d\n%d\n", tx, ty, maxval);
+                for (int y = ty - 1; y >= 0; y--)        // PGM rows run top-to-bottom: flip (image row 0 = bottom)
+                    for (int x = 0; x < tx; x++) {
+                        const unsigned v = std::min(fr[(size_t)y * tx + x], 65535u);
+                        if (maxval > 255) std::fputc((int)(v >> 8), f);      // 16-bit samples: most significant byte first
+                        std::fputc((int)(v & 255u), f);
+                    }
+                std::fclose(f);
+            }
+        } else {
+            CHECK(pt_render_until(ctx[0], 1, 0, batch, max_spp, noise_target, &done, &noise), ctx[0]);
+        }
         spp = done;
     } else {
         for (int k = 0; k < spp; k += chunk) {
@@ -379,6 +420,9 @@ int main(int argc, char** argv) {
         if (until)
             std::printf(", \"frames_done\": %d, \"noise_mean\": %.8f, \"noise_max\": %.8f, \"noise_above_frac\": %.8f",
                         spp, (double)noise.sum_q / npx / 65536.0, noise.max_q / 65536.0, (double)noise.above / npx);
+        if (adaptive)
+            std::printf(", \"tiles\": %llu, \"tiles_active\": %llu, \"pixel_frames\": %llu", astats.tiles,
+                        astats.tiles_active, astats.pixel_frames);
         std::printf("}\n");
     }
 

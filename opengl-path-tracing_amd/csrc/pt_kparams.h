@@ -73,6 +73,9 @@ struct KParams {
     int n_sweep;                   // ... its leaves (<= ptl::kSweepMaxLeaves)
     int sweep;                     // LDS scene, 256 threads: guarded rays sweep the leaf boxes instead of walking
     int sweep_root;                // ... after the root box's own test (the camera stands outside the root box)
+    // tiles in this launch's queue: the queue holds queue_tiles * n_groups * 64 ids.  The whole tile grid for every
+    // launch but an adaptive one (pt_render_adaptive), whose tile_perm lists only the tiles still active
+    unsigned queue_tiles;
 };
 
 struct Cnt {

@@ -89,7 +89,9 @@ static int plan_group(const SceneFacts& f, const Tuning& t, const Image& im, con
     if (t.group_force > 0) return std::min(t.group_force, n_frames);
     const bool lds_scene = lds_staged(f, t, im, s);
     const double lanes = (double)im.n_cu * 4.0 * resident_waves(t.minw, lds_scene) * 64.0;
-    const double px = (double)im.rows_local * im.width;
+    // (an adaptive launch renders the pixels of its active tiles only: few tiles make short items, so that the
+    // shortened queue still has an item for every resident wave)
+    const double px = s.adaptive ? (double)im.n_tiles * 64.0 : (double)im.rows_local * im.width;
     const double F = px * n_frames / lanes;
     int g = (int)(std::sqrt(F) * (lds_scene ? 0.416 : 0.19) + 0.5);
     g = std::max(1, std::min(g, lds_scene ? 16 : 4));
@@ -233,7 +235,7 @@ LaunchPlan plan_launch(const SceneFacts& f, const Tuning& t, const Image& im, co
     // ogl_path_trace.h:160-204) ends in a tail of nearly empty waves.  Its render kernel runs on an overlap slot (own
     // stream, colour scratch and queue counter) so the next render's waves fill the CUs that this one's tail frees
     // (enqueue_render). Not for captured graphs or counting.
-    p.overlap = t.overlap_slots > 1 && !graph && !s.counting && n_frames <= kShortLaunch && p.split;
+    p.overlap = t.overlap_slots > 1 && !graph && !s.counting && !s.adaptive && n_frames <= kShortLaunch && p.split;
     const size_t lds = p.lds ? (p.cons_walk ? f.lds_bytes_sk : f.lds_bytes) : 0;
     // the wide walk's workgroup: wider ones share one LDS copy of more top records (tuning key 17); raysPerPixel > 1
     // keeps 256 threads
@@ -281,7 +283,7 @@ LaunchPlan plan_launch(const SceneFacts& f, const Tuning& t, const Image& im, co
     // what k_render_sm stages: the scene copy, or the top records / nodes and the shading records
     p.dyn_lds_bytes = p.lds ? lds : (p.wide ? (size_t)p.wide_top * 48 : (size_t)p.n_top * 32) + shade_lds_bytes;
     p.key = kernel_key(s.counting, p.lds, p.wide, p.split, p.mw, im.rpp, p.nt, f.walk_np);
-    p.common = common_launch(f, t, im, p);
+    p.common = !s.adaptive && common_launch(f, t, im, p);
     // the sweep is in the 256-thread LDS lines only (a scene with a sweep table is far below the wide workgroups' sizes)
     p.sweep = p.lds && p.nt == 256 && sweep_on(f, t, s.counting);
     if (p.sweep && !t.shade_thresh) p.shade_thresh = kSweepShadeThresh;

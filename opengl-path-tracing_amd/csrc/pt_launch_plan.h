@@ -111,7 +111,13 @@ struct Image {
     unsigned persist_blocks;
     int tile_shift = 0;             // work-queue tiles of (8 << tile_shift) x (8 >> tile_shift) pixels (tuning key 20)
 };
-struct State { bool counting, moments, aces_fuse; };
+struct State {
+    bool counting, moments, aces_fuse;
+    // a launch of pt_render_adaptive: Image::n_tiles is its list of active tiles, not the grid.  A synchronous batch on
+    // the context's stream (no overlap slot) on the generic line of its key (the COMMON build writes tile costs
+    // unconditionally, and these launches record none)
+    bool adaptive = false;
+};
 
 // A k_render_sm instantiation by its template arguments (pt_render_kernels.h lists them).
 struct KernelKey { bool count, lds; int minw; bool multi, split, padn; int nt; bool wide; };

@@ -25,4 +25,14 @@ int pt_noise_host(const float* moments, const unsigned char* in_footprint, size_
     return PT_OK;
 }
 
+int pt_tile_retires_host(const float* moments, const unsigned char* in_footprint, size_t n_pixels, int frames,
+                         float target, int* retires) {
+    if (!retires) return PT_E_ARG;
+    pt_noise_stats s;
+    const int rc = pt_noise_host(moments, in_footprint, n_pixels, frames, target, &s);
+    if (rc) return rc;
+    *retires = ptn::tile_retires(s.sum_q, s.pixels, ptn::target_q(target)) ? 1 : 0;
+    return PT_OK;
+}
+
 }  // extern "C"

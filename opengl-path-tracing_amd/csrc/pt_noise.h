@@ -58,4 +58,12 @@ PTN_HD unsigned target_q(float target) {
     return (unsigned)(t * kQScale);
 }
 
+// The stop rule of adaptive sampling (pt_render_adaptive), per work-queue tile: the tile retires
+// once the sum of its footprint pixels' q is at most target_q times their number -- the
+// image-wide integer rule of pt_render_until on one tile.  sum_q <= 64 pixels * 2^22 and
+// target_q <= 2^22: the product cannot overflow 64 bits for any pixel count an image has.
+PTN_HD bool tile_retires(unsigned long long sum_q, unsigned long long pixels, unsigned tq) {
+    return sum_q <= (unsigned long long)tq * pixels;
+}
+
 }  // namespace ptn

@@ -1,7 +1,8 @@
 // pt_post_kernels.h -- a section of the pt_render.hip translation unit, not a general-purpose
 // header: pt_render.hip includes it once, after pt_kparams.h.
 // The small kernels around the render kernel: the progressive graph's frame counter, the
-// adaptive tile order, the frame-split mode's running mean, the tonemap and the noise summary.
+// adaptive tile order, the frame-split mode's running mean, the tonemap, the noise summary and
+// adaptive sampling's accumulate-and-retire pass.
 namespace {
 
 using pti::accumulate;
@@ -218,6 +219,148 @@ __global__ __launch_bounds__(256) void k_noise(KParams p, int frames, unsigned t
             atomicAdd(&out->above, (unsigned long long)above);
             atomicMax(&out->max_q, max_q);
         }
+    }
+}
+
+// Adaptive sampling (pt_render_adaptive): the accumulate pass and the stop rule
+// of one batch, over the launch's list of active tiles only.  The call's summary block: the
+// tiles retired so far (sums that only grow over the call) and the tiles that stay active after
+// this batch (zeroed by the stream before each batch, with the next list's length).
+struct AdaptSum {
+    unsigned long long ret_pixels, ret_sum_q, ret_above, ret_tiles, pixel_frames;
+    unsigned ret_max_q, pad;
+    unsigned long long act_pixels, act_sum_q, act_above;    // from here on: per batch
+    unsigned act_max_q, n_next;
+};
+struct AdaptArgs {
+    unsigned n_list;            // tiles in the launch's list (KParams::tile_perm, KParams::queue_tiles)
+    unsigned per_wave;          // tiles a wave takes in turn, 1..kAdaptTilesPerWave (adapt_tiles_per_wave)
+    int n_tiles;                // the tile grid (tile_frames' length)
+    int n_after;                // n0 + the frames done after this pass: the stop rule's n (0: a batch's earlier launch, no verdict)
+    unsigned frames_after;      // the frames this call has given the list's tiles after this pass
+    unsigned target_q;
+    unsigned* tile_frames;      // per tile of the grid: frames received in this call
+    unsigned* next;             // the tiles that stay active (any order)
+    AdaptSum* sum;
+};
+constexpr int kAdaptTilesPerWave = 8;
+// Tiles per wave for a list of n tiles: 8 for long lists (a set of summary atomics per 32 tiles), fewer for short
+// ones, whose pass is a chain of dependent loads per wave and not a stream (a list of 736 tiles took 139 us at 8 per
+// wave, the time of one wave's 8 tiles x 8 load groups): about 1,000 blocks at most either way.
+inline unsigned adapt_tiles_per_wave(unsigned n) { return std::min(8u, std::max(1u, n / 4096u)); }
+constexpr int kAdaptFrames = 8;   // frames per load group (as k_accum_frames' long shape), then one at a time
+// One wave per tile and turn; lane w owns the pixel the render kernel's queue id w of that tile
+// maps to (the same tw / th / tile_shift arithmetic and the same bounds), folds the batch's
+// colours from the scratch planes in frame order (pti::accumulate, ptn::add_sample: what
+// k_accum_frames<.., true> does for the pixel), stores image and moments, and quantises its own
+// pixel; the wave reduces.  A wave takes a.per_wave tiles in turn, four list entries apart, keeps
+// its sums in registers and its surviving tiles in LDS; at the end the block adds its four
+// waves' integers into the summary block and reserves its stretch of the next list -- one set
+// of atomics per block (32 tiles of a long list), not per tile (the lesson of k_noise).  Every field is an
+// integer: exact in any order.  A list entry outside the tile grid is skipped.
+__global__ __launch_bounds__(256) void k_accum_retire(KParams p, AdaptArgs a) {
+    const unsigned wave = threadIdx.x >> 6, w = threadIdx.x & 63u;
+    const int tsh = p.tile_shift, tw = 8 << tsh, th = 8 >> tsh;
+    const int tiles_x = (p.W + tw - 1) >> (3 + tsh);
+    const size_t n = (size_t)p.rows_local * (size_t)p.W;
+    unsigned long long r_sum = 0, a_sum = 0, pf = 0;
+    unsigned r_px = 0, r_ab = 0, r_mx = 0, r_tiles = 0, a_px = 0, a_ab = 0, a_mx = 0, n_surv = 0;
+    __shared__ unsigned s_surv[4][kAdaptTilesPerWave];
+    for (unsigned j = 0; j < a.per_wave && j < (unsigned)kAdaptTilesPerWave; j++) {    // (s_surv holds kAdaptTilesPerWave)
+        const unsigned li = (blockIdx.x * a.per_wave + j) * 4u + wave;
+        if (li >= a.n_list) break;              // wave-uniform
+        const unsigned pk = p.tile_perm[li];
+        const int tx = (int)(pk & 0xffffu), ty = (int)(pk >> 16);
+        const long long tile = (long long)ty * tiles_x + tx;
+        if (tx >= tiles_x || tile >= (long long)a.n_tiles) continue;     // wave-uniform: not a tile of this grid
+        const int cx = tx * tw + (int)(w & (unsigned)(tw - 1));
+        const int crow = ty * th + (int)(w >> (3 + tsh));
+        const bool on = cx < p.W && crow < p.rows_local && cx < p.x_limit && p.row0 + crow * p.row_stride < p.y_limit;
+        const size_t idx = on ? (size_t)crow * (size_t)p.W + (size_t)cx : 0;
+        float4 acc = (on && p.acc_first) ? p.accum[idx] : make_float4(0, 0, 0, 0);
+        float2 mom = (on && p.acc_first) ? p.moments[idx] : make_float2(0, 0);
+        int k = 0;
+        for (; k + kAdaptFrames <= p.n_frames; k += kAdaptFrames) {
+            f3 v[kAdaptFrames];
+#pragma unroll
+            for (int u = 0; u < kAdaptFrames; u++)
+                v[u] = on ? nt_load3(p.rgb + 3 * ((size_t)(k + u) * n + idx)) : mk(0, 0, 0);
+#pragma unroll
+            for (int u = 0; u < kAdaptFrames; u++) {
+                acc = accumulate(acc, v[u], p.frame_first + k + u, k + u > 0 || p.acc_first == 1);
+                ptn::add_sample(mom.x, mom.y, ptn::luminance(v[u].x, v[u].y, v[u].z));
+            }
+        }
+        for (; k < p.n_frames; k++) {
+            const f3 v = on ? nt_load3(p.rgb + 3 * ((size_t)k * n + idx)) : mk(0, 0, 0);
+            acc = accumulate(acc, v, p.frame_first + k, k > 0 || p.acc_first == 1);
+            ptn::add_sample(mom.x, mom.y, ptn::luminance(v.x, v.y, v.z));
+        }
+        if (on) {
+            p.accum[idx] = acc;
+            p.moments[idx] = mom;
+        }
+        unsigned px = on ? 1u : 0u;
+        for (int off = 32; off > 0; off >>= 1) px += __shfl_xor(px, off, 64);
+        pf += (unsigned long long)px * (unsigned long long)p.n_frames;
+        if (!a.n_after || !px) continue;        // wave-uniform: no verdict yet, or a tile without a footprint pixel
+        const unsigned q = on ? ptn::quantise(mom.x, mom.y, a.n_after) : 0u;
+        unsigned sq = q, ab = (on && q > a.target_q) ? 1u : 0u, mx = q;    // a tile's sum: at most 64 * 2^22
+        for (int off = 32; off > 0; off >>= 1) {
+            sq += __shfl_xor(sq, off, 64);
+            ab += __shfl_xor(ab, off, 64);
+            const unsigned o = __shfl_xor(mx, off, 64);
+            mx = o > mx ? o : mx;
+        }
+        if (w == 0) a.tile_frames[tile] = a.frames_after;
+        if (ptn::tile_retires(sq, px, a.target_q)) {
+            r_sum += sq, r_px += px, r_ab += ab, r_mx = mx > r_mx ? mx : r_mx, r_tiles++;
+        } else {
+            a_sum += sq, a_px += px, a_ab += ab, a_mx = mx > a_mx ? mx : a_mx;
+            if (w == 0) s_surv[wave][n_surv] = pk;
+            n_surv++;
+        }
+    }
+    // the block's four waves: their sums (every lane of a wave holds the wave's) through LDS
+    __shared__ unsigned long long s_u64[4][3];
+    __shared__ unsigned s_u32[4][8], s_base;
+    if (w == 0) {
+        s_u64[wave][0] = r_sum, s_u64[wave][1] = a_sum, s_u64[wave][2] = pf;
+        s_u32[wave][0] = r_px, s_u32[wave][1] = r_ab, s_u32[wave][2] = r_mx, s_u32[wave][3] = r_tiles;
+        s_u32[wave][4] = a_px, s_u32[wave][5] = a_ab, s_u32[wave][6] = a_mx, s_u32[wave][7] = n_surv;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned total = n_surv;
+        for (unsigned o = 1; o < 4; o++) {
+            r_sum += s_u64[o][0], a_sum += s_u64[o][1], pf += s_u64[o][2];
+            r_px += s_u32[o][0], r_ab += s_u32[o][1], r_tiles += s_u32[o][3], a_px += s_u32[o][4], a_ab += s_u32[o][5];
+            r_mx = s_u32[o][2] > r_mx ? s_u32[o][2] : r_mx;
+            a_mx = s_u32[o][6] > a_mx ? s_u32[o][6] : a_mx;
+            total += s_u32[o][7];
+        }
+        if (pf) atomicAdd(&a.sum->pixel_frames, pf);
+        if (r_tiles) {
+            atomicAdd(&a.sum->ret_pixels, (unsigned long long)r_px);
+            atomicAdd(&a.sum->ret_sum_q, r_sum);
+            atomicAdd(&a.sum->ret_above, (unsigned long long)r_ab);
+            atomicAdd(&a.sum->ret_tiles, (unsigned long long)r_tiles);
+            atomicMax(&a.sum->ret_max_q, r_mx);
+        }
+        if (total) {
+            atomicAdd(&a.sum->act_pixels, (unsigned long long)a_px);
+            atomicAdd(&a.sum->act_sum_q, a_sum);
+            atomicAdd(&a.sum->act_above, (unsigned long long)a_ab);
+            atomicMax(&a.sum->act_max_q, a_mx);
+            s_base = atomicAdd(&a.sum->n_next, total);     // the block's stretch of the next list
+        }
+    }
+    __syncthreads();
+    if (w == 0 && n_surv) {         // (n_surv > 0 in any wave means total > 0: s_base was written)
+        unsigned at = s_base;
+        for (unsigned o = 0; o < wave; o++) at += s_u32[o][7];
+        // at + n_surv <= the sum of all blocks' survivors <= n_list <= the list buffers' n_tiles entries
+        for (unsigned i = 0; i < n_surv; i++) a.next[at + i] = s_surv[wave][i];
     }
 }
 

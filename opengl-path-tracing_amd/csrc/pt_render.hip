@@ -143,6 +143,15 @@ struct pt_ctx {
     int mom_frames = 0;
     pt_noise_stats* d_noise = nullptr;
     pt_noise_stats* h_noise = nullptr;
+    // adaptive sampling (pt_render_adaptive): the moments hold per-tile frame counts since the last adaptive run
+    // (mom_frames is then the largest) until the image restarts; the per-tile frame map, the two lists of active
+    // tiles a batch reads and writes, and the call's summary block with its pinned host copy -- all sized by the tile
+    // grid and dropped with it (set_tiles)
+    bool mom_mixed = false;
+    unsigned* d_tile_frames = nullptr;
+    unsigned* d_active[2] = {nullptr, nullptr};
+    AdaptSum* d_adapt = nullptr;
+    AdaptSum* h_adapt = nullptr;
     std::string err;
 };
 
@@ -178,6 +187,10 @@ static int set_tiles(pt_ctx* c, int s) {
     (void)hipFree(c->d_tile_perm);
     (void)hipFree(c->d_tile_cost);
     c->d_tile_perm = c->d_tile_cost = nullptr;
+    (void)hipFree(c->d_tile_frames);      // the adaptive buffers are per tile: allocated again on first use
+    (void)hipFree(c->d_active[0]);
+    (void)hipFree(c->d_active[1]);
+    c->d_tile_frames = c->d_active[0] = c->d_active[1] = nullptr;
     std::vector<unsigned> ident(std::max(c->n_tiles, 1));
     for (size_t i = 0; i < ident.size(); i++) ident[i] = pack_tile(c, (unsigned)i);
     HIPCHK(c, hipMalloc(&c->d_tile_perm, ident.size() * sizeof(unsigned)));
@@ -269,6 +282,11 @@ void pt_destroy(pt_ctx* c) {
     if (c->h_noise) (void)hipHostFree(c->h_noise);
     (void)hipFree(c->d_tile_perm);
     (void)hipFree(c->d_tile_cost);
+    (void)hipFree(c->d_tile_frames);
+    (void)hipFree(c->d_active[0]);
+    (void)hipFree(c->d_active[1]);
+    (void)hipFree(c->d_adapt);
+    if (c->h_adapt) (void)hipHostFree(c->h_adapt);
     (void)hipFree(c->d_rgb);
     for (int i = 0; i < kMaxSlots; i++) {
         if (c->rstream[i]) (void)hipStreamSynchronize(c->rstream[i]);
@@ -619,6 +637,7 @@ static KParams fill_params(const pt_ctx* c, const ptl::LaunchPlan& pl, int frame
     p.compact_max = c->tun.compact_max;
     p.group = pl.group, p.pull_batch = pl.pull_batch, p.grp_magic = pl.grp_magic;
     p.tile_perm = c->d_tile_perm, p.tile_shift = c->tile_shift;
+    p.queue_tiles = (unsigned)c->n_tiles;
     p.tile_cost = (c->tun.adaptive && !c->counting) ? c->d_tile_cost : nullptr;
     return p;
 }
@@ -781,7 +800,7 @@ int pt_render_async(pt_ctx* c, int frame_first, int n_frames, int acc_first) {
     rc = enqueue_frames(c, frame_first, n_frames, acc_first, nullptr, 0);
     if (rc) return rc;
     if (c->moments) {   // the frames in the moments: they restart where the image does
-        if (!acc_first) c->mom_frames = 0;
+        if (!acc_first) c->mom_frames = 0, c->mom_mixed = false;
         c->mom_frames += n_frames;
     }
     HIPCHK(c, hipEventRecord(ev[1], c->stream));
@@ -852,7 +871,7 @@ int pt_progressive_reset(pt_ctx* c, int next_frame) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     // frame 1 restarts the image and the moments on the device (resolve_frames); any other
     // frame continues both
-    if (next_frame == 1) c->mom_frames = 0;
+    if (next_frame == 1) c->mom_frames = 0, c->mom_mixed = false;
     return PT_OK;
 }
 
@@ -994,6 +1013,7 @@ int pt_set_moments(pt_ctx* c, int enable) {
     HIPCHK(c, hipSetDevice(c->cfg.device));
     const size_t px = std::max<size_t>((size_t)c->rows_local * c->cfg.width, 1);
     c->mom_frames = 0;
+    c->mom_mixed = false;
     if ((enable != 0) == (c->moments != nullptr)) {
         // already so; on again: zeroed behind the passes that may still write them
         if (c->moments) HIPCHK(c, hipMemsetAsync(c->moments, 0, px * sizeof(float2), c->stream));
@@ -1039,6 +1059,7 @@ int pt_noise(pt_ctx* c, float target, pt_noise_stats* out) {
     if (!c || !out) return PT_E_ARG;
     if (!c->moments) return fail(c, PT_E_STATE, "moments are off (pt_set_moments)");
     if (c->mom_frames < 2) return fail(c, PT_E_STATE, "the noise estimate needs at least 2 frames");
+    if (c->mom_mixed) return fail(c, PT_E_STATE, "per-tile frame counts after pt_render_adaptive: no single n until the image restarts");
     HIPCHK(c, hipSetDevice(c->cfg.device));
     HIPCHK(c, hipMemsetAsync(c->d_noise, 0, sizeof(pt_noise_stats), c->stream));
     const long long px = (long long)c->rows_local * c->cfg.width;
@@ -1066,6 +1087,8 @@ int pt_render_until(pt_ctx* c, int frame_first, int acc_first, int batch, int ma
     if (batch < 2 || max_frames < batch || !(target > 0.0f))
         return fail(c, PT_E_ARG, "pt_render_until: batch >= 2, max_frames >= batch, target > 0");
     if (!c->scene_ok) return fail(c, PT_E_STATE, "pt_render_until before pt_upload_scene");
+    if (acc_first && c->moments && c->mom_mixed)
+        return fail(c, PT_E_STATE, "per-tile frame counts after pt_render_adaptive: pt_render_until must restart the image");
     if (!c->moments) {
         int rc = pt_set_moments(c, 1);
         if (rc) return rc;
@@ -1084,6 +1107,144 @@ int pt_render_until(pt_ctx* c, int frame_first, int acc_first, int batch, int ma
         if (s.sum_q <= tq * s.pixels) break;      // mean relative error at or below the target
     }
     if (last) *last = s;
+    return PT_OK;
+}
+
+// Adaptive sampling.  The buffers of the tile grid, on first use after set_tiles.
+static int ensure_adaptive(pt_ctx* c) {
+    const size_t bytes = (size_t)std::max(c->n_tiles, 1) * sizeof(unsigned);
+    if (!c->d_adapt) HIPCHK(c, hipMalloc(&c->d_adapt, sizeof(AdaptSum)));
+    if (!c->h_adapt) HIPCHK(c, hipHostMalloc((void**)&c->h_adapt, sizeof(AdaptSum), hipHostMallocDefault));
+    if (!c->d_tile_frames) {
+        HIPCHK(c, hipMalloc(&c->d_tile_frames, bytes));
+        HIPCHK(c, hipMemsetAsync(c->d_tile_frames, 0, bytes, c->stream));
+    }
+    for (unsigned*& l : c->d_active)
+        if (!l) HIPCHK(c, hipMalloc(&l, bytes));
+    return PT_OK;
+}
+
+// One launch of an adaptive batch on the context stream: the render kernel over the `n_list` tiles of `list` (the
+// generic line of the key the planner gives for that many tiles, no tile costs), then k_accum_retire over the same
+// list.  n_after != 0: the batch's last launch, which decides.
+static int enqueue_adaptive(pt_ctx* c, int frame_first, int n_frames, int acc_first, const unsigned* list, unsigned n_list,
+                            unsigned* next, int n_after, unsigned frames_after, unsigned target_q) {
+    ptl::Image im = plan_image(c);
+    im.n_tiles = (int)n_list;
+    ptl::State st = plan_state(c);
+    st.adaptive = true;
+    const ptl::LaunchPlan pl = ptl::plan_launch(c->sf, c->tun, im, st, n_frames, false);
+    if (!pl.split || pl.overlap || pl.common) return fail(c, PT_E_STATE, "internal: an adaptive launch must be a plain split launch");
+    KParams p = fill_params(c, pl, frame_first, n_frames, acc_first, nullptr, 0);
+    int rc = ensure_rgb(c, ptl::scratch_bytes(pl, plan_image(c), n_frames));   // full-image planes (aidx)
+    if (rc) return rc;
+    p.rgb = c->d_rgb;
+    p.tile_perm = list;
+    p.queue_tiles = n_list;
+    p.tile_cost = nullptr;
+    p.moments = c->moments;
+    if (pl.sweep && (!p.sweep_tab || p.n_sweep < 1 || p.n_sweep > ptl::kSweepMaxLeaves || 2 * p.n_sweep != p.n_slots))
+        return fail(c, PT_E_STATE, "internal: a sweeping launch without a sweep table");
+    const RenderKernel* kernel = find_kernel(pl.key, false, false);
+    if (!kernel) return fail(c, PT_E_STATE, "no k_render_sm instantiation for the adaptive launch's key");
+    c->last_swept = pl.sweep;
+    HIPCHK(c, hipMemsetAsync(c->d_work, 0, kQueueSet * sizeof(unsigned), c->stream));
+    hipLaunchKernelGGL(kernel->fn, dim3(pl.blocks), dim3((unsigned)kernel->key.nt), pl.dyn_lds_bytes, c->stream, p);
+    c->n_line_launches[0]++;
+    const unsigned per_wave = adapt_tiles_per_wave(n_list), per_block = 4u * per_wave;
+    AdaptArgs a = {n_list, per_wave, c->n_tiles, n_after, frames_after, target_q, c->d_tile_frames, next, c->d_adapt};
+    hipLaunchKernelGGL(k_accum_retire, dim3((n_list + per_block - 1) / per_block), dim3(256), 0, c->stream, p, a);
+    HIPCHK(c, hipGetLastError());
+    return PT_OK;
+}
+
+int pt_render_adaptive(pt_ctx* c, int frame_first, int acc_first, int batch, int max_frames, float target,
+                       int* frames_done, pt_adaptive_stats* last) {
+    if (!c || !frames_done) return PT_E_ARG;
+    *frames_done = 0;
+    if (batch < 2 || max_frames < batch || !(target > 0.0f))
+        return fail(c, PT_E_ARG, "pt_render_adaptive: batch >= 2, max_frames >= batch, target > 0");
+    if (!c->scene_ok) return fail(c, PT_E_STATE, "pt_render_adaptive before pt_upload_scene");
+    if (acc_first && c->moments && c->mom_mixed)
+        return fail(c, PT_E_STATE, "per-tile frame counts after pt_render_adaptive: the next adaptive call must restart the image");
+    if (!c->moments) {
+        int rc = pt_set_moments(c, 1);
+        if (rc) return rc;
+    }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    int rc = ensure_tiles(c);
+    if (rc) return rc;
+    rc = ensure_adaptive(c);
+    if (rc) return rc;
+    const int n0 = acc_first ? c->mom_frames : 0;
+    const unsigned tq = ptn::target_q(target);
+    const size_t tile_bytes = (size_t)std::max(c->n_tiles, 1) * sizeof(unsigned);
+    if (c->counting) HIPCHK(c, hipMemsetAsync(c->d_counters, 0, 16 * sizeof(unsigned long long), c->stream));
+    c->stage_ok = false;
+    c->aces_fuse = false;       // no ACES view from these passes: pt_present_begin runs its own
+    c->presented = false;
+    // the first list: every tile, in the learned order (behind the sorts on this stream; overlapped renders of
+    // earlier calls have been waited for by the accumulate passes on it)
+    HIPCHK(c, hipMemcpyAsync(c->d_active[0], c->d_tile_perm, tile_bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_tile_frames, 0, tile_bytes, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_adapt, 0, sizeof(AdaptSum), c->stream));
+    std::memset(c->h_adapt, 0, sizeof(AdaptSum));
+    unsigned n_list = c->rows_local > 0 ? (unsigned)c->n_tiles : 0u;
+    int done = 0, cur = 0;
+    while (done < max_frames && n_list > 0) {
+        const int n = std::min(batch, max_frames - done);
+        // the batch's share of the summary block: the tiles that stay active, and the next list's length
+        HIPCHK(c, hipMemsetAsync(&c->d_adapt->act_pixels, 0, sizeof(AdaptSum) - offsetof(AdaptSum, act_pixels), c->stream));
+        // a batch too large for the scratch budget or the 32-bit queue ids runs as several launches; the last decides
+        const int step = launch_frames(c, n);
+        for (int off = 0; off < n; off += step) {
+            const int m = std::min(step, n - off);
+            const bool decides = off + m >= n;
+            rc = enqueue_adaptive(c, frame_first + done + off, m, (done + off) ? 1 : acc_first, c->d_active[cur], n_list,
+                                  c->d_active[cur ^ 1], decides ? n0 + done + n : 0, (unsigned)(done + n), tq);
+            if (rc) return rc;
+        }
+        HIPCHK(c, hipMemcpyAsync(c->h_adapt, c->d_adapt, sizeof(AdaptSum), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        done += n;
+        c->mom_frames = n0 + done;      // the largest count; per tile from here on
+        c->mom_mixed = true;
+        if (c->h_adapt->n_next > n_list) return fail(c, PT_E_STATE, "internal: the active list grew");
+        n_list = c->h_adapt->n_next;
+        cur ^= 1;
+    }
+    if (done == 0) {    // a context without rows: nothing rendered, the (empty) state restarts like the image
+        if (!acc_first) c->mom_frames = 0, c->mom_mixed = false;
+    }
+    c->count_pending = c->counting;
+    *frames_done = done;
+    if (last) {
+        const AdaptSum& s = *c->h_adapt;
+        last->noise.pixels = s.ret_pixels + s.act_pixels;
+        last->noise.sum_q = s.ret_sum_q + s.act_sum_q;
+        last->noise.above = s.ret_above + s.act_above;
+        last->noise.max_q = std::max(s.ret_max_q, s.act_max_q);
+        last->noise.frames = n0 + done;
+        last->tiles = s.ret_tiles + s.n_next;
+        last->tiles_active = s.n_next;
+        last->pixel_frames = s.pixel_frames;
+    }
+    return pt_sync(c);
+}
+
+int pt_read_tile_frames(pt_ctx* c, unsigned* dst, int max_tiles, int* n_tiles, int* tiles_x) {
+    if (!c) return PT_E_ARG;
+    if (dst && max_tiles < c->n_tiles) return fail(c, PT_E_ARG, "tile frame buffer too small");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (n_tiles) *n_tiles = c->n_tiles;
+    if (tiles_x) *tiles_x = c->tiles_x;
+    if (dst && c->n_tiles > 0) {
+        if (c->d_tile_frames)
+            HIPCHK(c, hipMemcpy(dst, c->d_tile_frames, (size_t)c->n_tiles * sizeof(unsigned), hipMemcpyDeviceToHost));
+        else
+            std::memset(dst, 0, (size_t)c->n_tiles * sizeof(unsigned));
+    }
     return PT_OK;
 }
 

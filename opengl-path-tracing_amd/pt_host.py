@@ -66,6 +66,17 @@ class NoiseStats(C.Structure):
                     above_frac=int(self.above) / n)
 
 
+class AdaptiveStats(C.Structure):
+    """pt_adaptive_stats (include/pt_api.h): the summary of a pt_render_adaptive call."""
+    _fields_ = [("noise", NoiseStats), ("tiles", C.c_ulonglong), ("tiles_active", C.c_ulonglong),
+                ("pixel_frames", C.c_ulonglong)]
+
+    def as_dict(self):
+        """NoiseStats.as_dict of the noise summary, plus tiles, tiles_active and pixel_frames."""
+        return dict(self.noise.as_dict(), tiles=int(self.tiles), tiles_active=int(self.tiles_active),
+                    pixel_frames=int(self.pixel_frames))
+
+
 _lib = None
 _F = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 _I = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
@@ -141,6 +152,9 @@ def lib():
             "pt_noise_host": (ip, [_F, vp, C.c_size_t, ip, fp, C.POINTER(NoiseStats)]),
             "pt_render_until": (ip, [vp, ip, ip, ip, ip, fp, C.POINTER(ip), C.POINTER(NoiseStats)]),
             "pt_group_noise": (ip, [vp, fp, C.POINTER(NoiseStats)]),
+            "pt_render_adaptive": (ip, [vp, ip, ip, ip, ip, fp, C.POINTER(ip), C.POINTER(AdaptiveStats)]),
+            "pt_read_tile_frames": (ip, [vp, vp, ip, C.POINTER(ip), C.POINTER(ip)]),
+            "pt_tile_retires_host": (ip, [_F, vp, C.c_size_t, ip, fp, C.POINTER(ip)]),
             "pt_group_create": (ip, [C.POINTER(vp), ip, C.POINTER(vp)]),
             "pt_group_destroy": (None, [vp]),
             "pt_group_last_error": (C.c_char_p, [vp]),
@@ -526,6 +540,24 @@ class PathTracer:
                                           float(target), C.byref(done), C.byref(s)))
         return done.value, s.as_dict()
 
+    def render_adaptive(self, target, batch=16, max_frames=1024, frame_first=1, accumulate_first=0):
+        """pt_render_adaptive: frames in batches, each work-queue tile until its own mean relative
+        error is at most `target` (or max_frames) -> (frames_done, summary dict of
+        AdaptiveStats.as_dict)."""
+        done, s = C.c_int(), AdaptiveStats()
+        self._check(lib().pt_render_adaptive(self.h, int(frame_first), int(accumulate_first), int(batch),
+                                             int(max_frames), float(target), C.byref(done), C.byref(s)))
+        return done.value, s.as_dict()
+
+    def tile_frames(self):
+        """pt_read_tile_frames -> (tiles_y, tiles_x) uint32: the frames each tile of the work queue
+        received in the last render_adaptive (row 0 = the tiles of local row 0)."""
+        n, tx = C.c_int(), C.c_int()
+        self._check(lib().pt_read_tile_frames(self.h, None, 0, C.byref(n), C.byref(tx)))
+        out = np.zeros(max(n.value, 1), np.uint32)
+        self._check(lib().pt_read_tile_frames(self.h, out.ctypes.data, len(out), C.byref(n), C.byref(tx)))
+        return out[: n.value].reshape(-1, max(tx.value, 1))
+
     def diag(self):
         """Lane utilisation per kernel phase from the last counting render."""
         v = np.zeros(16, np.uint64)
@@ -714,6 +746,24 @@ def noise_host(moments, frames, target, in_footprint=None):
     if rc:
         raise PTError(rc, "pt_noise_host: frames must be >= 2")
     return s.as_dict()
+
+
+def tile_retires_host(moments, frames, target, in_footprint=None):
+    """pt_tile_retires_host: whether a tile of these (..., 2) float32 moments retires after
+    `frames` frames (the stop rule of render_adaptive, on the host; noise_host's arguments)."""
+    m = np.ascontiguousarray(moments, np.float32).reshape(-1)
+    n = m.size // 2
+    fp = None
+    if in_footprint is not None:
+        fp = np.ascontiguousarray(np.asarray(in_footprint).reshape(-1) != 0, np.uint8)
+        if fp.size != n:
+            raise ValueError("in_footprint must hold one flag per pixel")
+    r = C.c_int()
+    rc = lib().pt_tile_retires_host(m if n else np.zeros(2, np.float32), None if fp is None else fp.ctypes.data, n,
+                                    int(frames), float(target), C.byref(r))
+    if rc:
+        raise PTError(rc, "pt_tile_retires_host: frames must be >= 2")
+    return bool(r.value)
 
 
 def group_plan(devices, ranks):
