@@ -157,6 +157,9 @@ int pt_debug_window_cull(pt_ctx* ctx, int* active, float* slack);
  * ran it, *qualifies = 1 when the uploaded scene has a sweep table, *n_leaves = the scene's leaf
  * pairs.  Any pointer may be null. */
 int pt_debug_sweep(pt_ctx* ctx, int* swept, int* qualifies, int* n_leaves);
+/* The path pool (tuning key 24): *pooled = 1 when the render launch this context enqueued last
+ * ran the pool kernel of the specialised swept line.  The pointer may be null. */
+int pt_debug_pool(pt_ctx* ctx, int* pooled);
 /* The adaptive tile order (tuning key 2), read only: waits for the context's work, then
  * *sorts = the tile-order sorts run since the last scene upload (a captured graph's sorts count
  * once per replay), *n_tiles and *tiles_x = the work queue's tile grid (tuning key 20), and
@@ -231,6 +234,9 @@ int pt_set_kernel(pt_ctx* ctx, int variant);
  * key 23 = leaf sweep (0 = automatic, 1 = off: the culling walk).  In a scene of a few leaves
  *         a ray inside the exact-reciprocal guard tests every leaf box once per segment, with
  *         bounds that are the same for all lanes, instead of walking the tree ("The leaf sweep").
+ * key 24 = path pool (0 = automatic, 1 = off).  Launches of the specialised swept line that run on the
+ *         context's own stream (every launch but an overlapped short one, key 9) keep the path
+ *         state in a per-wave LDS pool and hand any path to any lane.
  * None of these change the image (each pixel's frames stay in order in one lane). */
 int pt_set_tuning(pt_ctx* ctx, int key, int value);
 

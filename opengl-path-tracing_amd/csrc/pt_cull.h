@@ -247,7 +247,10 @@ PT_HD unsigned sweep_push(unsigned m, bool hit) {
 #endif
 }
 // The candidate mask of a ray inside the guard: bit k is set when the box of sweep-table entry k passes at t0.
-// table: 2 quads per entry, {lo.x, hi.x, lo.y, hi.y}, {lo.z, hi.z, pair, 0} (ptp::kSweep), indexable by int; n <= 32.
+// table: 2 quads per entry, {lo.x, hi.x, lo.y, hi.y}, {lo.z, hi.z, pair, inverse} (ptp::kSweep), indexable by int;
+// n <= 32.  Entry k is the k-th leaf of the chain: its own box, axis-paired as the reference's node records (what
+// pti::slab_fast reads: k_render_pool stages these records for its exact leaf re-test), and its triangle-pair index;
+// `inverse` of entry p is the chain position of pair p (both render kernels stage the triangle slots by it).
 // The boxes run from the last to the first so that a set bit enters as the carry of mask + mask.
 // (Requesting box k - 1's bounds before box k's test measured 0.5% slower on C2 than this plain loop: the other
 // resident waves already cover the scalar loads' latency.)

@@ -3,6 +3,8 @@
 // invariants the kernel relies on.
 #include "pt_launch_plan.h"
 
+#include "pt_pool.h"
+
 #include "../../include/pt_api.h"
 
 #include <algorithm>
@@ -287,6 +289,29 @@ LaunchPlan plan_launch(const SceneFacts& f, const Tuning& t, const Image& im, co
     // the sweep is in the 256-thread LDS lines only (a scene with a sweep table is far below the wide workgroups' sizes)
     p.sweep = p.lds && p.nt == 256 && sweep_on(f, t, s.counting);
     if (p.sweep && !t.shade_thresh) p.shade_thresh = kSweepShadeThresh;
+    {
+        // The path pool: the specialised swept line only, not on an overlap slot (below), the
+        // packed fields of a path hold this launch (pt_pool.h; the bounce limit is enqueue_render's to check), and the
+        // pools and the trimmed scene -- triangle slots, materials, the sphere, the leaf boxes -- fit the CU's LDS.
+        // Workgroups per CU: what the LDS holds (1 KiB below the even share, for the allocation granule), at most
+        // kPoolWaves waves per SIMD, the kernel's register budget.  The condition is the overlap slot, not the launch's
+        // length: a launch of 1 to 16 frames on the context's stream (a captured graph's, or with key 9 = 1) pools, and
+        // gains (same-process A/B against k_render_sm with key 9 = 1, 1080p Cornell: 1-frame launches +18.8%, 4-frame
+        // +4.3%, 16-frame +5.0%, 64-frame +5.6%); overlapped launches were not measured with the pool.  The pool runs only at that occupancy, the one
+        // its constants were measured at: one wave per SIMD fewer already loses to k_render_sm (128 x 256 at 3 waves:
+        // -5% on C2), so a scene whose trimmed copy costs a workgroup per CU (more than about 5.6 KB) keeps k_render_sm.
+        p.pool_paths = kPoolPaths, p.pool_nt = kPoolThreads;
+        const int wpb = kPoolThreads / 64;
+        const size_t scene = (size_t)(4 * f.n_slots + 3 * f.n_mats + 2 * f.n_spheres + 2 * f.n_leaves) * 16;
+        p.pool_lds_bytes = ptpool::block_bytes(kPoolPaths, wpb, scene);
+        const int full_cu = 4 * kPoolWaves / wpb;
+        const int per_cu = (int)std::min<size_t>(kLdsCu / (p.pool_lds_bytes + 1024), (size_t)full_cu);
+        p.pool = kPoolDefault && !t.pool_off && p.common && p.sweep && !p.overlap && per_cu >= 1 && per_cu == full_cu &&
+                 ptpool::pack_ok(im.width, im.rows_local, n_frames, 0, f.n_slots, f.n_spheres);
+        const unsigned long long paths = (unsigned long long)im.n_tiles * n_groups * 64ull, per_block = (unsigned long long)(kPoolPaths * wpb);
+        p.pool_blocks = (unsigned)std::min<unsigned long long>((unsigned long long)std::max(per_cu, 1) * (unsigned long long)std::max(im.n_cu, 1),
+                                                               std::max(1ull, (paths + per_block - 1) / per_block));
+    }
     if (p.split) {  // the accumulate pass: the long variant loads 8 frames per group
         p.accum_long = n_frames > kShortLaunch;
         p.accum_moments = s.moments;

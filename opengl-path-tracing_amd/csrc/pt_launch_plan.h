@@ -57,6 +57,29 @@ static_assert(kSweepMaxLeaves >= 1 && kSweepMaxLeaves <= 32, "a lane's candidate
 #define PT_SWEEP_SHADE_THRESH 56
 #endif
 constexpr int kSweepShadeThresh = PT_SWEEP_SHADE_THRESH;
+// The path pool of the specialised swept line (pt_pool.h): paths per wave, threads per workgroup and
+// the resident waves per SIMD its kernel is built for.  A pool costs 80 B of LDS per path, so the paths per wave trade
+// lane use against resident waves.  Same-process A/B against the swept line of k_render_sm (7 waves per SIMD), C2's
+// 1024-frame launch / the 1080p/8 share (profiles/ab/r13_path_pool/ab_table.txt; noise floor 0.3% / 0.5%), as
+// paths x threads (waves per CU): 64x256 (24) -8.9% / -11.4%, 80x256 (20) +0.5 / -1.8, 96x256 (16) +1.5 / -0.3,
+// 128x256 (12) -5.0 / -7.6, 128x448 (14) +2.6 / -0.5, 112x512 (16) +8.5 / +5.7, 116x512 (16) +9.4 / +6.6, 112x1024
+// (16) +8.9, 120x1024 (16) +10.0 on C2 (one workgroup per CU: not measured on the share); 96x576 (18 waves in two
+// nine-wave workgroups) -28%.  116 paths is the most that two 512-thread workgroups hold beside their scene copies.
+// PT_POOL_* override the values for A/B builds.
+#ifndef PT_POOL_PATHS
+#define PT_POOL_PATHS 116
+#endif
+#ifndef PT_POOL_THREADS
+#define PT_POOL_THREADS 512
+#endif
+#ifndef PT_POOL_WAVES
+#define PT_POOL_WAVES 4
+#endif
+#ifndef PT_POOL_DEFAULT
+#define PT_POOL_DEFAULT 1      // 0: builds without the pool as default (A/B)
+#endif
+constexpr int kPoolPaths = PT_POOL_PATHS, kPoolThreads = PT_POOL_THREADS, kPoolWaves = PT_POOL_WAVES;
+constexpr bool kPoolDefault = PT_POOL_DEFAULT != 0;
 
 // What ptp::pack_scene (pt_scene_pack.h) learns about a scene (pt_ctx holds one by value).
 struct SceneFacts {
@@ -103,6 +126,7 @@ struct Tuning {
     int common_off = 0;             // key 21: 1 = never the specialised default-path kernel (LaunchPlan::common)
     int win_off = 0;                // key 22: 1 = the culling walk without its window clause (pt_cull.h)
     int sweep_off = 0;              // key 23: 1 = no leaf sweep (the culling walk instead)
+    int pool_off = 0;               // key 24: 1 = no path pool (k_render_sm's swept line instead)
 };
 
 // the context's share of the image and its device; what else a launch depends on
@@ -141,6 +165,14 @@ struct LaunchPlan {
     // Guarded rays sweep the scene's leaf boxes instead of walking (pt_cull.h, sweep_mask).  The COMMON line is built
     // with it on and with it off; a generic LDS line reads it as a kernel argument.
     bool sweep;
+    // The launch may run k_render_pool (pt_render_pool.h) instead of the COMMON swept line: path state in a
+    // wave-private LDS pool of pool_paths paths, pool_nt threads per workgroup, pool_blocks workgroups of
+    // pool_lds_bytes dynamic LDS each.  Beside the generic fields, which keep their values: enqueue_render takes the
+    // line they describe when a fact only it can see fails (common_params_ok, the bounce limit of the packing).
+    bool pool;
+    int pool_paths, pool_nt;
+    unsigned pool_blocks;
+    size_t pool_lds_bytes;
 };
 
 // The template arguments of the one line built with COMMON (the default path of a Cornell-sized scene).

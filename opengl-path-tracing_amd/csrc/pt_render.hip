@@ -25,6 +25,7 @@
 #include "pt_launch_plan.h"
 #include "pt_math.h"
 #include "pt_noise.h"
+#include "pt_pool.h"
 #include "pt_render_kernels.h"
 #include "pt_scene_pack.h"
 #include "pt_wide.h"
@@ -48,6 +49,7 @@ using ptl::kPullBatch;
 // The device half, as sections of this translation unit (one compile, one set of kernel symbols):
 #include "pt_kparams.h"        // DevScene, KParams, Cnt, SceneView, the queue-head stride
 #include "pt_render_sm.h"      // k_render_sm: scene access, the leaf tests, the three walks, the state machine
+#include "pt_render_pool.h"    // k_render_pool: the swept line with the path state in a per-wave LDS pool
 #include "pt_post_kernels.h"   // k_advance_frames, k_tile_order, k_accum_frames, k_aces, k_noise
 
 // ===================================================================== host side
@@ -125,6 +127,7 @@ struct pt_ctx {
     unsigned long long n_line_launches[2] = {0, 0};   // render launches enqueued on a generic / a COMMON line (pt_debug_launches)
     bool count_pending = false;
     bool last_swept = false;        // the last render launch enqueued ran the leaf sweep (pt_debug_sweep)
+    bool last_pooled = false;       // ... ran k_render_pool (pt_debug_pool)
     // asynchronous presentation (pt_present_begin / _end): per buffer a pinned host image and
     // its copy event; the device view is rgba8 (one, as the copies and the passes that write
     // it are ordered on the context stream)
@@ -411,6 +414,7 @@ static const TuningKey kTuningKeys[] = {
     {21, &ptl::Tuning::common_off, in_0_1, "specialised default-path kernel: 0 = automatic, 1 = off", true},
     {22, &ptl::Tuning::win_off, in_0_1, "window clause of the culling walk: 0 = automatic, 1 = off", true},
     {23, &ptl::Tuning::sweep_off, in_0_1, "leaf sweep: 0 = automatic, 1 = off", true},
+    {24, &ptl::Tuning::pool_off, in_0_1, "path pool: 0 = automatic, 1 = off", true},
 };
 
 int pt_set_tuning(pt_ctx* c, int key, int value) {
@@ -682,6 +686,10 @@ static int enqueue_render(pt_ctx* c, int frame_first, int n_frames, int acc_firs
         return fail(c, PT_E_STATE, "internal: a sweeping launch without a sweep table");
     const RenderKernel* kernel = find_kernel(pl.key, common, pl.sweep);
     c->last_swept = pl.sweep;
+    // the path pool: the plan's `pool` on the specialised swept line, and the bounce count its packing holds
+    const bool pool = pl.pool && common && pl.sweep &&
+                      ptpool::pack_ok(p.W, p.rows_local, n_frames, p.max_bounce, p.n_slots, p.sc.n_spheres);
+    c->last_pooled = pool;
     if (!kernel) {
         const ptl::KernelKey& k = pl.key;
         char key[96];
@@ -696,7 +704,11 @@ static int enqueue_render(pt_ctx* c, int frame_first, int n_frames, int acc_firs
     // the slot's creation)
     if (pl.overlap) p.reset_work = work;
     else HIPCHK(c, hipMemsetAsync(work, 0, kQueueSet * sizeof(unsigned), rs));
-    hipLaunchKernelGGL(kernel->fn, dim3(pl.blocks), dim3((unsigned)kernel->key.nt), pl.dyn_lds_bytes, rs, p);
+    if (pool)
+        hipLaunchKernelGGL((k_render_pool<ptl::kPoolThreads, ptl::kPoolPaths, ptl::kPoolWaves>), dim3(pl.pool_blocks),
+                           dim3((unsigned)pl.pool_nt), pl.pool_lds_bytes, rs, p);
+    else
+        hipLaunchKernelGGL(kernel->fn, dim3(pl.blocks), dim3((unsigned)kernel->key.nt), pl.dyn_lds_bytes, rs, p);
     c->n_line_launches[common]++;
     if (pl.split) {
         if (pl.overlap) {
@@ -1148,6 +1160,7 @@ static int enqueue_adaptive(pt_ctx* c, int frame_first, int n_frames, int acc_fi
     const RenderKernel* kernel = find_kernel(pl.key, false, false);
     if (!kernel) return fail(c, PT_E_STATE, "no k_render_sm instantiation for the adaptive launch's key");
     c->last_swept = pl.sweep;
+    c->last_pooled = false;
     HIPCHK(c, hipMemsetAsync(c->d_work, 0, kQueueSet * sizeof(unsigned), c->stream));
     hipLaunchKernelGGL(kernel->fn, dim3(pl.blocks), dim3((unsigned)kernel->key.nt), pl.dyn_lds_bytes, c->stream, p);
     c->n_line_launches[0]++;
@@ -1397,6 +1410,12 @@ int pt_debug_sweep(pt_ctx* c, int* swept, int* qualifies, int* n_leaves) {
     if (swept) *swept = c->last_swept ? 1 : 0;
     if (qualifies) *qualifies = c->sf.sweep_ok ? 1 : 0;
     if (n_leaves) *n_leaves = c->sf.n_leaves;
+    return PT_OK;
+}
+
+int pt_debug_pool(pt_ctx* c, int* pooled) {
+    if (!c) return PT_E_ARG;
+    if (pooled) *pooled = c->last_pooled ? 1 : 0;
     return PT_OK;
 }
 

@@ -1,0 +1,344 @@
+// pt_render_pool.h -- a section of the pt_render.hip translation unit, included after pt_render_sm.h.
+// k_render_pool: the specialised swept line (LaunchPlan::common && sweep) with the path state in a wave-private LDS
+// pool instead of registers (pt_pool.h).  A wave owns P paths and two ready lists; every pass it pops
+// up to 64 paths of the longer list, one per lane, loads the fields the phase reads, runs the phase of k_render_sm on
+// them -- the same per-ray functions on the same values -- stores what changed and pushes each path to the list of
+// its new state.  The order in which paths are served cannot show in the image: every frame's colour goes to the
+// frame-split scratch, and k_accum_frames applies the running mean in frame order.
+// No cross-wave communication: the only barrier follows the scene staging; list heads and counts are wave-uniform.
+// TWIN: the SHADE body (finish segment, queue pull, camera ray, segment set-up) and the swept LEAF body below restate
+// those of k_render_sm (pt_render_sm.h) with COMMON && SWEEP folded in, so that the existing kernels keep their device
+// code.  A change to the shading, the queue protocol or the leaf choice there must be made here too; only the bitwise
+// GPU tests (tests/test_gpu_path_pool.py: pool on against pool off against the oracle) catch drift between the two.
+namespace {
+
+// The reference walk and leaf tests for a ray outside the exact-reciprocal guard (a few thousand of C2's segments),
+// from global memory inside the set-up pass: the IEEE-division slab on the reference's node records and each lane's
+// own triangle tests, as the generic global-memory line runs them.  The triangles are read from the LDS copy, whose
+// slots are in chain order (pair q at chain position sweep_tab[2 q + 1].w), so hprim is an index of that copy.
+__device__ __forceinline__ void pool_cold_walk(const KParams& p, const SceneView& S, f3 o, f3 d, float& t, int& hprim) {
+    int w = 0;
+    while (w >= 0) {
+        const float4 lo = p.sc.nodes[2 * w], hi = p.sc.nodes[2 * w + 1];
+        const int a = __float_as_int(hi.z), b = __float_as_int(hi.w);
+        if (!slab(lo, hi, o, d, t)) { w = b; continue; }
+        if (a >= 0) { w = a; continue; }
+        const int q = (~a) >> 2;                                        // the leaf's pair
+        const int s0 = 2 * __float_as_int(p.sweep_tab[2 * q + 1].w);    // its slots in the chain-order copy
+        const bool cop = __float_as_int(tri_quad<true>(S, s0 + 1, 1).w) != 0;
+        const float4 nda = tri_quad<true>(S, s0, 0);
+        const float4 ndb = cop ? nda : tri_quad<true>(S, s0 + 1, 0);
+        const float ta = tri_plane(nda, o, d);
+        const float tb = cop ? ta : tri_plane(ndb, o, d);
+        bool oka = false, okb = false, ca = false, cb = false;
+        if (win_open(ta, t)) oka = tri_edges_at<true, false>(S, s0, mk(nda.x, nda.y, nda.z), o + d * ta, false, 0.0f, ca);
+        if (win_closed(tb, t)) okb = tri_edges_at<true, false>(S, s0 + 1, mk(ndb.x, ndb.y, ndb.z), o + d * tb, false, 0.0f, cb);
+        const float h1 = oka ? ta : -1.0f, h2 = okb ? tb : -1.0f;
+        const bool c1 = win_open(h1, t) & ((h1 < h2) | (h2 < 0.0001f));
+        const bool c2 = !c1 & win_open(h2, t);
+        if (c1 | c2) {
+            t = c1 ? h1 : h2;
+            hprim = s0 + (c1 ? 0 : 1);
+        }
+        w = b;
+    }
+}
+
+// Orders a pass's LDS stores before the next pass's loads for the compiler (one wave: the hardware keeps LDS
+// operations of a wave in order).
+__device__ __forceinline__ void pool_pass_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <int NT, int P, int MINW>
+__global__ __launch_bounds__(NT, MINW) void k_render_pool(KParams p) {
+    static_assert(P >= 64 && P <= ptpool::kMaxPaths && P % 4 == 0, "one-byte list entries in a 16-byte padded array");
+    using namespace ptpool;
+    const const_v4f* const sweep_tab = (const const_v4f*)(size_t)p.sweep_tab;
+    resolve_frames(p);
+    extern __shared__ float4 lds[];
+    // staged: what swept rays read -- the triangle slots in chain order (planes), materials, the sphere, and the
+    // leaf boxes for the exact re-test (the sweep table's own records: axis-paired, chain order)
+    const int T = p.n_slots, nt = 4 * T, nm = 3 * p.n_mats, ns = 2, nb = 2 * p.n_sweep;
+    for (int i = threadIdx.x; i < nt; i += NT) {
+        const int slot = i >> 2, c = __float_as_int(p.sweep_tab[2 * (slot >> 1) + 1].w);
+        lds[(i & 3) * T + 2 * c + (slot & 1)] = p.sc.tris[i];
+    }
+    for (int i = threadIdx.x; i < nm; i += NT) lds[nt + i] = p.sc.mats[i];
+    for (int i = threadIdx.x; i < ns; i += NT) lds[nt + nm + i] = p.sc.spheres[i];
+    for (int i = threadIdx.x; i < nb; i += NT) lds[nt + nm + ns + i] = p.sweep_tab[i];
+    const int scene_q = nt + nm + ns + nb;
+    const int lane = (int)(threadIdx.x & 63u);
+    float4* const pool = lds + scene_q + (int)(threadIdx.x >> 6) * (wave_bytes(P) / 16);
+    unsigned char* const list = (unsigned char*)(pool + kChunks * P);
+    for (int i = lane; i < P; i += kLanes) {    // every path starts fresh (t < 0) and without a work item
+        pool[quad_of(kChunkO, i, P)] = make_float4(0, 0, 0, -1.0f);
+        pool[quad_of(kChunkD, i, P)] = make_float4(0, 0, 1, 0);
+        pool[quad_of(kChunkInc, i, P)] = make_float4(0, 0, 0, __uint_as_float(pack_hit(-1, -1)));
+        pool[quad_of(kChunkCol, i, P)] = make_float4(1, 1, 1, 0);
+        pool[quad_of(kChunkItem, i, P)] = make_float4(__uint_as_float(kNoItem), 0, 0, 0);
+        list[i] = (unsigned char)i;
+    }
+    __syncthreads();
+    SceneView S;
+    S.nodes = nullptr;
+    S.tris = lds;
+    S.mats = lds + nt;
+    S.spheres = lds + nt + nm;
+    const float4* const boxes = lds + nt + nm + ns;
+    S.np = 0;
+    S.tp = T;
+    S.cm[0] = p.cons_m[0], S.cm[1] = p.cons_m[1], S.cm[2] = p.cons_m[2];
+    S.ws[0] = p.win_slack[0], S.ws[1] = p.win_slack[1], S.ws[2] = p.win_slack[2];
+    S.clo = ptc::kWindowLo;
+    const f3 cpos = mk(p.cam[0], p.cam[1], p.cam[2]), cfwd = mk(p.cam[3], p.cam[4], p.cam[5]);
+    const f3 cright = mk(p.cam[6], p.cam[7], p.cam[8]), cup = mk(p.cam[9], p.cam[10], p.cam[11]);
+    const int tiles_x = (p.W + 7) >> 3;
+    const unsigned n_groups = (unsigned)((p.n_frames + p.group - 1) / p.group);
+    const unsigned total_ids = p.queue_tiles * n_groups * 64u;
+    unsigned qnext = 0, qend = 0;     // the wave's reserved queue ids
+    Lists L = {P, 0};
+    while (L.nS + L.nL > 0) {
+        const int phase = choose(L), n = take(L, phase);
+        const bool on = lane < n;
+        int idx = 0;
+        if (on) idx = list[pop_index(L, phase, n, lane, P)];
+        drop(L, phase, n);
+        bool to_shade = false, to_leaf = false;
+        if (phase == kShade) {
+            // ---------------- SHADE: finish segment, regenerate, set up the next segment (k_render_sm's, COMMON)
+            const float4 c0 = pool[quad_of(kChunkO, idx, P)], c1 = pool[quad_of(kChunkD, idx, P)];
+            const float4 c2 = pool[quad_of(kChunkInc, idx, P)], c3 = pool[quad_of(kChunkCol, idx, P)];
+            const float4 c4 = pool[quad_of(kChunkItem, idx, P)];
+            f3 o = mk(c0.x, c0.y, c0.z), d = mk(c1.x, c1.y, c1.z), inc = mk(c2.x, c2.y, c2.z), col = mk(c3.x, c3.y, c3.z);
+            float t = c0.w;
+            unsigned bi = __float_as_uint(c1.w);
+            int hprim = hit_hprim(__float_as_uint(c2.w)), bounce = hit_bounce(__float_as_uint(c2.w));
+            uint32_t state = __float_as_uint(c3.w);
+            unsigned xy = __float_as_uint(c4.x);
+            int aidx = __float_as_int(c4.y);
+            int k = k_k(__float_as_uint(c4.z)), kend = k_kend(__float_as_uint(c4.z));
+            unsigned pcost = cost_of(__float_as_uint(c4.w));
+            bool report = cost_report(__float_as_uint(c4.w));
+            bool retired = false;
+            if (on && !(t < 0.0f)) {   // a finished segment (t < 0: fresh)
+                const bool hit = hprim != -1;
+                pcost++;
+                bool finished = false;
+                f3 rgb = inc;
+                if (hit && pt::length_gt_001(col)) {
+                    const f3 hitp = o + d * t;
+                    f3 normal;
+                    int mat;
+                    if (hprim >= 0) {
+                        const float4 nq = tri_quad<true>(S, hprim, 0);
+                        normal = mk(nq.x, nq.y, nq.z);
+                        mat = __float_as_int(tri_quad<true>(S, hprim, 2).w);
+                    } else {
+                        const int si = -2 - hprim;
+                        float4 s0 = S.spheres[2 * si];
+                        normal = pt::normalize(hitp - mk(s0.x, s0.y, s0.z));
+                        mat = __float_as_int(S.spheres[2 * si + 1].x);
+                    }
+                    if (pt::dot(normal, d) > 0.0f) normal = normal * -1.0f;
+                    o = hitp;
+                    f3 diffuse = pt::normalize(normal + pt::random_unit_vector(state));
+                    float kk = 2.0f * pt::dot(normal, d);
+                    f3 specular = pt::normalize(d - normal * kk);
+                    float4 m0 = S.mats[3 * mat], m1 = S.mats[3 * mat + 1], m2 = S.mats[3 * mat + 2];
+                    float is_spec = (m1.w > pt::random01(state)) ? 1.0f : 0.0f;
+                    d = pt::mix(diffuse, specular, m0.w * is_spec);
+                    inc = inc + mk(m1.x, m1.y, m1.z) * col;
+                    col = col * pt::mix(mk(m0.x, m0.y, m0.z), mk(m2.x, m2.y, m2.z), is_spec);
+                    bounce++;
+                    if (bounce > p.max_bounce) {
+                        rgb = inc;
+                        finished = true;
+                    }
+                } else {
+                    f3 dir = pt::normalize(d);
+                    float tt = 0.5f * (dir.z + 1.0f);
+                    float omt = 1.0f - tt;
+                    f3 env = mk(omt * 1.0f + tt * 0.5f, omt * 1.0f + tt * 0.7f, omt * 1.0f + tt * 1.0f);
+                    rgb = inc + env * col;
+                    finished = true;
+                }
+                if (finished) {
+                    bounce = -1;
+                    const f3 px = (mk(0, 0, 0) + rgb) / 1.0f;
+                    nt_store3(p.rgb + 3 * ((size_t)k * (size_t)(p.rows_local * p.W) + (size_t)aidx), px);
+                    k++;
+                }
+                t = -1.0f;
+            }
+            if (on & (bounce < 0) & (xy != kNoItem) & (k >= kend)) {
+                if (report) atomicAdd(&p.tile_cost[(xy_crow(xy) >> 3) * tiles_x + (xy_lx(xy) >> 3)], pcost);
+                xy = kNoItem;
+            }
+            // wave-aggregated pull from the work queue (k_render_sm's protocol)
+            const bool want = on && xy == kNoItem;
+            const unsigned long long m = __ballot(want);
+            if (m) {
+                const unsigned need = (unsigned)__popcll(m);
+                const unsigned rank = (unsigned)rank_in(m);
+                const int leader = __ffsll((long long)m) - 1;
+                unsigned id;
+                if (qend - qnext >= need) {
+                    id = qnext + rank;
+                    qnext += need;
+                } else {
+                    const unsigned avail = qend - qnext;
+                    const unsigned take_ids = max(need - avail, (unsigned)p.pull_batch);
+                    unsigned base = 0;
+                    if (want && rank == 0u) base = atomicAdd(p.work_counter, take_ids);
+                    base = (unsigned)__builtin_amdgcn_readlane((int)base, leader);
+                    id = rank < avail ? qnext + rank : base + (rank - avail);
+                    qnext = base + (need - avail);
+                    qend = base + take_ids;
+                }
+                if (want) {
+                    if (id >= total_ids) {
+                        retired = true;      // the queue is empty: the path retires
+                    } else {
+                        const unsigned item = id >> 6, w = id & 63u;
+                        const unsigned tile = p.grp_magic ? __umulhi(item, p.grp_magic) : item;
+                        const int g = (int)(item - tile * n_groups);
+                        const unsigned pk = p.tile_perm[tile];
+                        const int tx = (int)(pk & 0xffffu), ty = (int)(pk >> 16);
+                        const int cx = tx * 8 + (int)(w & 7u);
+                        const int crow = ty * 8 + (int)(w >> 3);
+                        if ((cx < p.W) & (crow < p.rows_local)) {
+                            xy = pack_xy(cx, crow);
+                            aidx = crow * p.W + cx;
+                            report = (w & 0x1bu) == 0u;
+                            pcost = 0;
+                            k = g * p.group;
+                            kend = min(k + p.group, p.n_frames);
+                            bounce = -1;
+                        }
+                    }
+                }
+            }
+            if (on && xy != kNoItem) {
+                const int lx = xy_lx(xy), y = p.row0 + xy_crow(xy) * p.row_stride;
+                if (bounce < 0) {    // camera ray due
+                    state = pt::seed(lx, y, p.frame_first + k);
+                    const float ax = pt::random01(state);
+                    const float ay = pt::random01(state);
+                    float u = pt::div_mk((float)lx + ax, p.fW, p.rW) - 0.5f;
+                    float v = pt::div_mk((float)y + ay, p.fH, p.rH) - 0.5f;
+                    d = pt::normalize((cfwd + cright * u) + cup * v);
+                    o = cpos;
+                    inc = mk(0, 0, 0);
+                    col = mk(1, 1, 1);
+                    bounce = 0;
+                }
+                const bool fast_seg =
+                       in_guard(o.x, 0x1p-40f, 0x1p60f) & in_guard(o.y, 0x1p-40f, 0x1p60f) &
+                       in_guard(o.z, 0x1p-40f, 0x1p60f) & in_range_abs(d.x, 0x1p-20f, 2.0f) &
+                       in_range_abs(d.y, 0x1p-20f, 2.0f) & in_range_abs(d.z, 0x1p-20f, 2.0f);
+                const f3 rd = fast_seg ? mk(pt::rcp_fast(d.x), pt::rcp_fast(d.y), pt::rcp_fast(d.z)) : mk(0, 0, 0);
+                t = __builtin_huge_valf();
+                hprim = -1;
+                {
+                    float4 s0 = S.spheres[0];
+                    f3 oc = o - mk(s0.x, s0.y, s0.z);
+                    float a = pt::dot(d, d);
+                    float half_b = pt::dot(oc, d);
+                    float cq = pt::dot(oc, oc) - s0.w;
+                    float disc = half_b * half_b - a * cq;
+                    float ht = disc < 0.0f ? -1.0f : (-half_b - pt::sqrt_g(disc)) / a;
+                    if (win_open(ht, t)) {
+                        t = ht;
+                        hprim = -2;
+                    }
+                }
+                const bool walk = !ray_has_nan(o, d);     // (a sweeping launch has nodes and triangles)
+                unsigned cand = 0u;
+                if (walk & fast_seg) {
+                    f3 ol, oh;
+                    ptc::cull_addends(o, rd, S.cm, S.ws, ol, oh);
+                    const ptc::SweepRay sr = ptc::sweep_ray(rd, ol, oh);
+                    bool in = true;
+                    if (p.sweep_root) in = ptc::sweep_root_hit(p.root_box, sr, t, S.clo);
+                    if (in) cand = ptc::sweep_mask(sr, t, S.clo, sweep_tab, p.n_sweep);
+                }
+                // rays outside the guard: cold code, the whole reference walk here (wave-uniform branch)
+                const bool cold = walk & !fast_seg;
+                if (__any(cold)) {
+                    if (cold) pool_cold_walk(p, S, o, d, t, hprim);
+                }
+                bi = cand;
+                to_leaf = cand != 0u;
+            }
+            to_shade = on & !retired & !to_leaf;
+            if (on) {
+                pool[quad_of(kChunkO, idx, P)] = make_float4(o.x, o.y, o.z, t);
+                pool[quad_of(kChunkD, idx, P)] = make_float4(d.x, d.y, d.z, __uint_as_float(bi));
+                pool[quad_of(kChunkInc, idx, P)] = make_float4(inc.x, inc.y, inc.z, __uint_as_float(pack_hit(hprim, bounce)));
+                pool[quad_of(kChunkCol, idx, P)] = make_float4(col.x, col.y, col.z, __uint_as_float(state));
+                pool[quad_of(kChunkItem, idx, P)] = make_float4(__uint_as_float(xy), __int_as_float(aidx),
+                                                                __uint_as_float(pack_k(k, kend)),
+                                                                __uint_as_float(pack_cost(pcost, report)));
+            }
+        } else {
+            // ---------------- LEAF: the lowest candidate's pair tests, the 2-way choice, the exact re-test
+            const float4 c0 = pool[quad_of(kChunkO, idx, P)], c1 = pool[quad_of(kChunkD, idx, P)];
+            float* const hw = (float*)&pool[quad_of(kChunkInc, idx, P)] + 3;
+            const unsigned hb = __float_as_uint(*hw);
+            const f3 o = mk(c0.x, c0.y, c0.z), d = mk(c1.x, c1.y, c1.z);
+            float t = c0.w;
+            unsigned bi = __float_as_uint(c1.w);
+            const bool at = on;
+            int s0 = 0, lp = 0;
+            bool cop = false;
+            float4 nd0 = make_float4(0, 0, 0, 0);
+            if (at) {
+                lp = __ffs((int)bi) - 1;
+                s0 = 2 * lp;
+                cop = __float_as_int(tri_quad<true>(S, s0 + 1, 1).w) != 0;
+                nd0 = tri_quad<true>(S, s0, 0);
+            }
+            float h1 = -1.0f, h2 = -1.0f;
+            bool ca = false, cb = false;
+            leaf_pair_tests<true, false>(S, at, s0, nd0, cop, o, d, t, p.compact_max, h1, h2, false, ca, cb);
+            bool c1h = false, c2h = false;
+            if (at) {
+                c1h = win_open(h1, t) & ((h1 < h2) | (h2 < 0.0001f));
+                c2h = !c1h & win_open(h2, t);
+            }
+            // the sweep's test is conservative: the leaf's box passes the exact test at this t, or no triangle moves t
+            const bool chk = at & (c1h | c2h);
+            if (__any(chk)) {
+                if (chk) {
+                    const f3 rd = mk(pt::rcp_fast(d.x), pt::rcp_fast(d.y), pt::rcp_fast(d.z));
+                    if (!slab_fast(boxes[2 * lp], boxes[2 * lp + 1], o, d, rd, t)) c1h = c2h = false;
+                }
+            }
+            if (at) {
+                int hprim = hit_hprim(hb);
+                if (c1h | c2h) {
+                    t = c1h ? h1 : h2;
+                    hprim = s0 + (c1h ? 0 : 1);
+                }
+                bi &= bi - 1u;
+                to_leaf = bi != 0u;
+                to_shade = bi == 0u;
+                ((float*)&pool[quad_of(kChunkO, idx, P)])[3] = t;
+                ((float*)&pool[quad_of(kChunkD, idx, P)])[3] = __uint_as_float(bi);
+                *hw = __uint_as_float(with_hprim(hb, hprim));
+            }
+        }
+        // push: each path to the list of its new state
+        const unsigned long long mS = __ballot(to_shade), mL = __ballot(to_leaf);
+        if (to_shade) list[push_index(L, kShade, rank_in(mS), P)] = (unsigned char)idx;
+        if (to_leaf) list[push_index(L, kLeaf, rank_in(mL), P)] = (unsigned char)idx;
+        grow(L, kShade, __popcll(mS));
+        grow(L, kLeaf, __popcll(mL));
+        pool_pass_fence();
+    }
+}
+
+}  // namespace

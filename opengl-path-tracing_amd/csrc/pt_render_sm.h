@@ -253,6 +253,9 @@ __device__ __forceinline__ void leaf_pair_tests(const SceneView& S, bool at, int
 // With the leaf sweep (scenes of a few leaves, pt_cull.h) a ray inside the guard never enters
 // TRAV: its segment set-up leaves the candidate leaves as a bit mask in bi, and the lane stays
 // in LEAF until the mask is empty.
+// TWIN: k_render_pool (pt_render_pool.h) restates the SHADE body and the swept LEAF body of the COMMON && SWEEP line
+// on path state held in LDS.  A change to the shading, the queue protocol or the leaf choice here must be made there
+// too; tests/test_gpu_path_pool.py compares the two kernels word for word.
 // =====================================================================================
 enum : int { ST_DONE = 0, ST_TRAV = 1, ST_LEAF = 2, ST_SHADE = 3 };
 #ifndef PT_WALK_UNROLL

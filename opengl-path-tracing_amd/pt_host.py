@@ -139,6 +139,7 @@ def lib():
             "pt_debug_launches": (ip, [vp, np.ctypeslib.ndpointer(np.uint64)]),
             "pt_debug_window_cull": (ip, [vp, C.POINTER(ip), C.POINTER(fp)]),
             "pt_debug_sweep": (ip, [vp, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]),
+            "pt_debug_pool": (ip, [vp, C.POINTER(ip)]),
             "pt_debug_tile_order": (ip, [vp, C.POINTER(C.c_ulonglong), vp, ip, C.POINTER(ip), C.POINTER(ip)]),
             "pt_set_tuning": (ip, [vp, ip, ip]),
             "pt_progressive_setup": (ip, [vp, ip, ip]),
@@ -433,6 +434,19 @@ class PathTracer:
         if fn is not None:
             self._check(fn(self.h, C.byref(a), C.byref(q), C.byref(n)))
         return dict(swept=bool(a.value), qualifies=bool(q.value), n_leaves=int(n.value))
+
+    def set_pool(self, enable):
+        """Tuning key 24: the per-wave path pool of the specialised swept line.  Never
+        changes the image."""
+        self._check(lib().pt_set_tuning(self.h, 24, 0 if enable else 1))
+
+    def pooled(self):
+        """pt_debug_pool -> the last render launch ran the path-pool kernel."""
+        a = C.c_int()
+        fn = getattr(lib(), "pt_debug_pool", None)      # (an older build loaded with PT_LIB_PARTIAL has none)
+        if fn is not None:
+            self._check(fn(self.h, C.byref(a)))
+        return bool(a.value)
 
     def tile_order(self):
         """pt_debug_tile_order -> dict(sorts: tile-order sorts since the scene upload, n_tiles, tiles_x:

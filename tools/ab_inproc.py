@@ -103,7 +103,8 @@ def main():
     base = statistics.median(res[libs[0]])
     for l in libs:
         m = statistics.median(res[l])
-        print("%-8s median %9.1f  best %9.1f  (%+.2f%% vs %s)" % (l, m, max(res[l]), 100.0 * (m / base - 1.0), libs[0]))
+        pooled = " pooled" if getattr(pts[l], "pooled", lambda: False)() else ""    # (the last launch: k_render_pool)
+        print("%-8s median %9.1f  best %9.1f  (%+.2f%% vs %s)%s" % (l, m, max(res[l]), 100.0 * (m / base - 1.0), libs[0], pooled))
     for pt in pts.values():
         pt.close()
 
