@@ -332,6 +332,52 @@ int pt_read_tile_frames(pt_ctx* ctx, unsigned* dst, int max_tiles, int* n_tiles,
 int pt_tile_retires_host(const float* moments, const unsigned char* in_footprint, size_t n_pixels, int frames,
                          float target, int* retires);
 
+/* Denoised view: an edge-avoiding a-trous filter of the accumulation image, guided
+ * by first-hit normal, albedo and distance and, with moments of n >= 2 frames, by the per-pixel
+ * variance of the mean luminance (after pt_render_adaptive: with each tile's own frame count).
+ * A view only: the image, the moments and every launch stay what they are without it.
+ *
+ * iterations 1..8 (iteration i takes its 5x5 taps 1 << i pixels apart), guide_frames >= 1 (frames
+ * averaged into the guides), and one sigma per factor; a NaN or non-positive sigma switches its
+ * factor off.  Defaults: 5, 4, and 8 / 0.1 / 0.1 / 0.05. */
+typedef struct {
+    int iterations;
+    int guide_frames;
+    float sigma_lum, sigma_normal, sigma_albedo, sigma_depth;
+} pt_denoise_params;
+void pt_denoise_defaults(pt_denoise_params* params);
+typedef struct {
+    int guided;            /* 1: the luminance factor ran (moments on, n >= 2 frames) */
+    int guides_rendered;   /* 1: this call rendered the guides, 0: it found them cached */
+    int iterations;
+    int frames;            /* n of the moments (the largest after an adaptive run), 0 when they are off */
+} pt_denoise_info;
+/* Filters the image as of the renders issued so far, on the context stream behind their
+ * accumulate passes (as pt_present_begin), and waits.  params NULL = the defaults; info may be
+ * NULL.  The guides are the images pt_render(1, guide_frames, 0) would produce in display modes
+ * 2, 3 and 4 with the context's scene, camera, flags and rays per pixel; they are rendered by the
+ * first call and kept until pt_upload_scene, pt_set_camera or another guide_frames.  Pixels
+ * outside the dispatch footprint (PT_FLAG_REF_DISPATCH) are copied through.
+ * PT_E_STATE: before an upload, or on a row-split context (world > 1: its interleaved rows have
+ * no neighbours; denoising a pt_group is out of scope).  PT_E_ARG: iterations or guide_frames
+ * out of range. */
+int pt_denoise(pt_ctx* ctx, const pt_denoise_params* params, pt_denoise_info* info);
+/* Same, enqueued without waiting (pt_sync, or a read below, waits). */
+int pt_denoise_async(pt_ctx* ctx, const pt_denoise_params* params, pt_denoise_info* info);
+/* The last denoise's result: width * height * 4 floats, rgb filtered, alpha the image's.
+ * PT_E_STATE: no denoise yet. */
+int pt_read_denoised_rgba32f(pt_ctx* ctx, float* host_dst, size_t bytes);
+/* ... and its ACES-tonemapped RGBA8, computed on the device (as pt_read_rgba8_aces). */
+int pt_read_denoised_rgba8_aces(pt_ctx* ctx, unsigned char* host_dst, size_t bytes);
+/* The guides of the last denoise, 8 floats per pixel: N.rgb, Z, A.rgb, 0.  PT_E_STATE: no denoise yet. */
+int pt_read_guides(pt_ctx* ctx, float* host_dst, size_t bytes);
+/* The filter on the host: image W*H*4 floats, variance W*H floats of the mean luminance's
+ * variance (NULL = unguided), guides W*H*8 floats as pt_read_guides, in_footprint one byte per
+ * pixel (NULL = all), out W*H*4 floats.  No device is touched: the per-tap code is the device
+ * kernel's own.  PT_E_ARG: a null pointer, a size <= 0 or parameters out of range. */
+int pt_denoise_host(const float* image, const float* variance, const float* guides, const unsigned char* in_footprint,
+                    int W, int H, const pt_denoise_params* params, float* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -59,7 +59,11 @@ static void usage() {
                  "  --json          print a JSON summary line (with --noise-target also frames_done,\n"
                  "                  noise_mean, noise_max, noise_above_frac; with --adaptive also tiles,\n"
                  "                  tiles_active, pixel_frames)\n"
-                 "  --gpu-bvh       build the BVH on GPU 0 (pt_bvh_build_gpu; the same nodes)\n");
+                 "  --gpu-bvh       build the BVH on GPU 0 (pt_bvh_build_gpu; the same nodes)\n"
+                 "  --denoise       after rendering, filter the image (pt_api.h: pt_denoise; one context) with\n"
+                 "                  --denoise-iters N iterations (default 5) over guides of --guide-frames G\n"
+                 "                  frames (default 4); --denoise-pfm F / --denoise-ppm F write the result as\n"
+                 "                  the RGBA32F PFM / the ACES PPM; --json gains a \"denoise\" object\n");
 }
 
 // Checkpoint of a progressive render (SURVEY.md §5 checkpoint / resume): the running mean
@@ -188,6 +192,12 @@ int main(int argc, char** argv) {
     bool until = false, adaptive = false;
     std::string spp_map;
     pt_adaptive_stats astats = {{0, 0, 0, 0, 0}, 0, 0, 0};
+    bool denoise = false;
+    pt_denoise_params dparams;
+    pt_denoise_defaults(&dparams);
+    pt_denoise_info dinfo = {0, 0, 0, 0};
+    std::string denoise_pfm, denoise_ppm;
+    double denoise_ms = 0.0;
     for (int i = 3; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&](void) -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
@@ -213,12 +223,25 @@ int main(int argc, char** argv) {
         else if (a == "--max-spp") max_spp = std::atoi(next());
         else if (a == "--json") json = true;
         else if (a == "--gpu-bvh") gpu_bvh = true;
+        else if (a == "--denoise") denoise = true;
+        else if (a == "--denoise-iters") dparams.iterations = std::atoi(next());
+        else if (a == "--guide-frames") dparams.guide_frames = std::atoi(next());
+        else if (a == "--denoise-pfm") denoise_pfm = next();
+        else if (a == "--denoise-ppm") denoise_ppm = next();
         else { usage(); return 2; }
     }
     if (ranks == 0) ranks = gpus;
     if (spp < 1 || chunk < 1 || gpus < 1 || ranks < 1) { usage(); return 2; }
     if (events && (!resume.empty() || !checkpoint.empty())) {
         std::fprintf(stderr, "--events excludes --resume / --checkpoint\n");
+        return 2;
+    }
+    if (denoise && (gpus > 1 || ranks > 1)) {     // a row-split context has no neighbouring rows to filter over
+        std::fprintf(stderr, "--denoise excludes --gpus / --ranks above 1\n");
+        return 2;
+    }
+    if (!denoise && (!denoise_pfm.empty() || !denoise_ppm.empty())) {
+        std::fprintf(stderr, "--denoise-pfm / --denoise-ppm need --denoise\n");
         return 2;
     }
     if (adaptive && !until) {
@@ -395,6 +418,17 @@ int main(int argc, char** argv) {
         for (int k = 0; k < rows; k++)
             std::memcpy(&rgba[4 * (size_t)(r0 + k * rs) * W], &part8[4 * (size_t)k * W], 4 * (size_t)W);
     }
+    std::vector<float> dimg;
+    std::vector<unsigned char> drgba;
+    if (denoise) {    // the filtered view of the finished image (the image itself stays as rendered)
+        auto td = std::chrono::steady_clock::now();
+        CHECK(pt_denoise(ctx[0], &dparams, &dinfo), ctx[0]);
+        denoise_ms = std::chrono::duration<double>(std::chrono::steady_clock::now() - td).count() * 1e3;
+        dimg.assign(4 * (size_t)W * H, 0.0f);
+        drgba.assign(4 * (size_t)W * H, 0);
+        CHECK(pt_read_denoised_rgba32f(ctx[0], dimg.data(), dimg.size() * 4), ctx[0]);
+        CHECK(pt_read_denoised_rgba8_aces(ctx[0], drgba.data(), drgba.size()), ctx[0]);
+    }
     pt_group_destroy(group);
     for (int g = 0; g < nctx; g++) pt_destroy(ctx[g]);
     std::printf("rendered %dx%d, %d spp, %d bounces on %d GPU(s), %d context(s): %.3f s, %.3f ms/frame\n", W, H, spp,
@@ -423,7 +457,26 @@ int main(int argc, char** argv) {
         if (adaptive)
             std::printf(", \"tiles\": %llu, \"tiles_active\": %llu, \"pixel_frames\": %llu", astats.tiles,
                         astats.tiles_active, astats.pixel_frames);
+        if (denoise)
+            std::printf(", \"denoise\": {\"guided\": %d, \"guides_rendered\": %d, \"iterations\": %d, "
+                        "\"guide_frames\": %d, \"frames\": %d, \"ms\": %.4f}",
+                        dinfo.guided, dinfo.guides_rendered, dinfo.iterations, dparams.guide_frames, dinfo.frames, denoise_ms);
         std::printf("}\n");
+    }
+    if (denoise && !denoise_pfm.empty()) {
+        FILE* f = std::fopen(denoise_pfm.c_str(), "wb");
+        if (!f) { std::fprintf(stderr, "cannot write %s\n", denoise_pfm.c_str()); return 1; }
+        std::fprintf(f, "PF\n%d %d\n-1.0\n", W, H);
+        for (size_t i = 0; i < (size_t)W * H; i++) std::fwrite(&dimg[4 * i], 4, 3, f);
+        std::fclose(f);
+    }
+    if (denoise && !denoise_ppm.empty()) {
+        FILE* f = std::fopen(denoise_ppm.c_str(), "wb");
+        if (!f) { std::fprintf(stderr, "cannot write %s\n", denoise_ppm.c_str()); return 1; }
+        std::fprintf(f, "P6\n%d %d\n255\n", W, H);
+        for (int y = H - 1; y >= 0; y--)
+            for (int x = 0; x < W; x++) std::fwrite(&drgba[4 * ((size_t)y * W + x)], 1, 3, f);
+        std::fclose(f);
     }
 
     if (FILE* f = std::fopen(pfm.c_str(), "wb")) {       // PFM rows run bottom-to-top: no flip

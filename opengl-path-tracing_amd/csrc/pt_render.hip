@@ -21,6 +21,7 @@
 //   mat   48 B : {color.rgb, smoothness}, {emission*strength, specProb}, {specular.rgb, 0}
 //   sphere 32 B: {c.xyz, r*r}, {matIdx, 0, 0, 0}
 #include "pt_cull.h"
+#include "pt_denoise_launch.h"
 #include "pt_isect.h"
 #include "pt_launch_plan.h"
 #include "pt_math.h"
@@ -155,6 +156,20 @@ struct pt_ctx {
     unsigned* d_active[2] = {nullptr, nullptr};
     AdaptSum* d_adapt = nullptr;
     AdaptSum* h_adapt = nullptr;
+    int adapt_done = 0;             // frames_done of the adaptive call the per-tile counts are from
+    // denoised view (pt_denoise): the two guide planes (N.rgb, Z) and (A.rgb, 0) with the guide_frames
+    // they hold, the filter's ping-pong state planes, its result and the result's ACES view.  The three rendered
+    // guide images pass through dn_state[0], dn_state[1] and dn_out on their way into the guide planes.
+    float4* dn_guide[2] = {nullptr, nullptr};
+    float4* dn_state[2] = {nullptr, nullptr};
+    float4* dn_out = nullptr;
+    uchar4* dn_rgba8 = nullptr;
+    bool guides_ok = false, dn_done = false;
+    int guides_frames = 0;
+    int dn_variant = 0;             // ptd::Variant (pt__denoise_debug; measurements only)
+    bool dn_timing = false;         // ... and events around the guide render, the prep and every iteration
+    hipEvent_t dn_ev[ptd::kMaxIterations + 3] = {};
+    int dn_ev_n = 0;
     std::string err;
 };
 
@@ -290,6 +305,11 @@ void pt_destroy(pt_ctx* c) {
     (void)hipFree(c->d_active[1]);
     (void)hipFree(c->d_adapt);
     if (c->h_adapt) (void)hipHostFree(c->h_adapt);
+    (void)hipFree(c->dn_guide[0]); (void)hipFree(c->dn_guide[1]);
+    (void)hipFree(c->dn_state[0]); (void)hipFree(c->dn_state[1]);
+    (void)hipFree(c->dn_out); (void)hipFree(c->dn_rgba8);
+    for (hipEvent_t e : c->dn_ev)
+        if (e) (void)hipEventDestroy(e);
     (void)hipFree(c->d_rgb);
     for (int i = 0; i < kMaxSlots; i++) {
         if (c->rstream[i]) (void)hipStreamSynchronize(c->rstream[i]);
@@ -338,6 +358,7 @@ int pt_upload_scene(pt_ctx* c, const float* tris, int n_tris, const float* bvh, 
     c->order_skip = 0;
     c->n_sorts = 0;
     c->scene_ok = true;
+    c->guides_ok = false;         // the guides are of the old scene
     return PT_OK;
 }
 
@@ -352,6 +373,7 @@ int pt_set_camera(pt_ctx* c, const float cam[12]) {
     float v[12] = {pos.x, pos.y, pos.z, fwd.x, fwd.y, fwd.z, right.x, right.y, right.z, up.x, up.y, up.z};
     std::memcpy(c->cam, v, sizeof(v));
     c->cam_ok = true;
+    c->guides_ok = false;         // ... or of the old camera
     drop_graph(c);
     return PT_OK;
 }
@@ -974,6 +996,7 @@ int pt__scene_replicate_layout(pt_ctx* dst, const pt_ctx* src, void* dptr[ptp::k
     dst->order_sorted = false;
     dst->order_skip = 0;
     dst->n_sorts = 0;
+    dst->guides_ok = false;
     // scene_ok stays false until the caller has filled the buffers (pt__scene_set_ready): a
     // failed broadcast or copy must not leave a context rendering from uninitialised memory
     dst->scene_ok = false;
@@ -1222,6 +1245,7 @@ int pt_render_adaptive(pt_ctx* c, int frame_first, int acc_first, int batch, int
         done += n;
         c->mom_frames = n0 + done;      // the largest count; per tile from here on
         c->mom_mixed = true;
+        c->adapt_done = done;
         if (c->h_adapt->n_next > n_list) return fail(c, PT_E_STATE, "internal: the active list grew");
         n_list = c->h_adapt->n_next;
         cur ^= 1;
@@ -1259,6 +1283,190 @@ int pt_read_tile_frames(pt_ctx* c, unsigned* dst, int max_tiles, int* n_tiles, i
             std::memset(dst, 0, (size_t)c->n_tiles * sizeof(unsigned));
     }
     return PT_OK;
+}
+
+// ---------------------------------------------------------------- denoised view
+// One launch of a guide render on the context stream: the render kernel in display mode `mode` over the whole tile
+// grid, then the plain accumulate pass into `plane` instead of the image.  Planned like an adaptive launch -- a
+// frame-split launch on the generic line of its key, on the context's own stream, never counting -- and invisible to
+// the context: no tile costs, no moments, no ACES view, no timing events, and none of the launch bookkeeping
+// (pt_debug_launches, pt_debug_sweep, pt_debug_pool, the sort cadence) moves.
+static int enqueue_guide(pt_ctx* c, const ptl::State& st, int mode, int frame_first, int n_frames, int acc_first, float4* plane) {
+    const ptl::Image im = plan_image(c);
+    const ptl::LaunchPlan pl = ptl::plan_launch(c->sf, c->tun, im, st, n_frames, false);
+    if (!pl.split || pl.overlap || pl.common) return fail(c, PT_E_STATE, "internal: a guide launch must be a plain split launch");
+    KParams p = fill_params(c, pl, frame_first, n_frames, acc_first, nullptr, 0);
+    int rc = ensure_rgb(c, ptl::scratch_bytes(pl, im, n_frames));
+    if (rc) return rc;
+    p.rgb = c->d_rgb;
+    p.accum = plane;
+    p.mode = mode;
+    p.tile_cost = nullptr;
+    p.moments = nullptr;
+    // (fill_params decides the window clause with the context's counting flag; a guide launch never counts)
+    p.win_lo = ptl::window_cull_on(c->sf, c->tun, c->cfg.flags, false) ? ptc::kWindowLo : -__builtin_huge_valf();
+    if (pl.sweep && (!p.sweep_tab || p.n_sweep < 1 || p.n_sweep > ptl::kSweepMaxLeaves || 2 * p.n_sweep != p.n_slots))
+        return fail(c, PT_E_STATE, "internal: a sweeping launch without a sweep table");
+    const RenderKernel* kernel = find_kernel(pl.key, false, false);
+    if (!kernel) return fail(c, PT_E_STATE, "no k_render_sm instantiation for the guide launch's key");
+    HIPCHK(c, hipMemsetAsync(c->d_work, 0, kQueueSet * sizeof(unsigned), c->stream));
+    hipLaunchKernelGGL(kernel->fn, dim3(pl.blocks), dim3((unsigned)kernel->key.nt), pl.dyn_lds_bytes, c->stream, p);
+    const KParamsKernel acc = pl.accum_long ? k_accum_frames<kAccumPixLong, kAccumFramesLong> : k_accum_frames<kAccumPix, 1>;
+    hipLaunchKernelGGL(acc, dim3(pl.accum_blocks), dim3(256), 0, c->stream, p);
+    HIPCHK(c, hipGetLastError());
+    return PT_OK;
+}
+
+// The guide planes of `frames` frames: display modes 2, 3 and 4 rendered as pt_render(1, frames, 0) would, each into a
+// zeroed plane (pixels outside the dispatch footprint stay zero), then packed.
+static int render_guides(pt_ctx* c, int frames) {
+    const size_t bytes = (size_t)c->rows_local * c->cfg.width * sizeof(float4);
+    float4* raw[3] = {c->dn_state[0], c->dn_state[1], c->dn_out};
+    ptl::State st = {false, true, false};   // not counting; split as with the moments on (the pass below keeps none)
+    st.adaptive = true;
+    for (int m = 0; m < 3; m++) {
+        HIPCHK(c, hipMemsetAsync(raw[m], 0, bytes, c->stream));
+        int done = 0;
+        while (done < frames) {
+            const int n = ptl::launch_frames(c->sf, c->tun, plan_image(c), st, frames - done);
+            int rc = enqueue_guide(c, st, 2 + m, 1 + done, n, done ? 1 : 0, raw[m]);
+            if (rc) return rc;
+            done += n;
+        }
+    }
+    ptd::launch_pack(c->stream, raw[0], raw[1], raw[2], c->dn_guide[0], c->dn_guide[1],
+                     (long long)c->rows_local * c->cfg.width);
+    HIPCHK(c, hipGetLastError());
+    return PT_OK;
+}
+
+int pt_denoise_async(pt_ctx* c, const pt_denoise_params* params, pt_denoise_info* info) {
+    if (!c) return PT_E_ARG;
+    pt_denoise_params dp;
+    pt_denoise_defaults(&dp);
+    if (params) dp = *params;
+    if (dp.iterations < 1 || dp.iterations > ptd::kMaxIterations) return fail(c, PT_E_ARG, "pt_denoise: iterations must be 1..8");
+    if (dp.guide_frames < 1) return fail(c, PT_E_ARG, "pt_denoise: guide_frames must be >= 1");
+    if (!c->scene_ok) return fail(c, PT_E_STATE, "pt_denoise before pt_upload_scene");
+    if (c->cfg.world > 1)
+        return fail(c, PT_E_STATE, "pt_denoise on a row-split context: its interleaved rows have no neighbours (groups are out of scope)");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    const size_t px = (size_t)c->rows_local * c->cfg.width;     // world == 1: every row
+    if (!c->dn_out) {
+        float4** planes[5] = {&c->dn_guide[0], &c->dn_guide[1], &c->dn_state[0], &c->dn_state[1], &c->dn_out};
+        for (float4** pl : planes)
+            if (!*pl) HIPCHK(c, hipMalloc(pl, px * sizeof(float4)));
+    }
+    if (c->dn_timing)
+        for (hipEvent_t& e : c->dn_ev)
+            if (!e) HIPCHK(c, hipEventCreate(&e));
+    int ev = 0;
+    const auto mark = [&]() { if (c->dn_timing) (void)hipEventRecord(c->dn_ev[ev++], c->stream); };
+    mark();
+    const bool render = !c->guides_ok || c->guides_frames != dp.guide_frames;
+    if (render) {
+        c->guides_ok = false;
+        c->dn_done = false;     // (the rendered planes pass through the result's plane)
+        int rc = render_guides(c, dp.guide_frames);
+        if (rc) return rc;
+        c->guides_ok = true;
+        c->guides_frames = dp.guide_frames;
+    }
+    mark();
+    const bool guided = c->moments != nullptr && c->mom_frames >= 2;
+    ptd::Image im;
+    {
+        KParams p;
+        fill_image(p, c);
+        im = {p.W, p.H, p.x_limit, p.y_limit};
+    }
+    const bool per_tile = guided && c->mom_mixed && c->d_tile_frames;
+    ptd::launch_prep(c->stream, im, c->accum, guided ? c->moments : nullptr, c->mom_frames,
+                     per_tile ? c->d_tile_frames : nullptr, c->mom_frames - c->adapt_done, c->tile_shift, c->tiles_x,
+                     c->dn_state[0]);
+    mark();
+    const ptd::K k = {ptd::inv_sq(dp.sigma_lum), ptd::inv_sq(dp.sigma_normal), ptd::inv_sq(dp.sigma_albedo),
+                      ptd::inv_sq(dp.sigma_depth)};
+    for (int i = 0; i < dp.iterations; i++) {
+        const bool last = i + 1 == dp.iterations;
+        ptd::launch_iter(c->stream, im, c->dn_state[i & 1], last ? c->dn_out : c->dn_state[(i + 1) & 1], c->dn_guide[0],
+                         c->dn_guide[1], last ? c->accum : nullptr, 1 << i, guided, k, c->dn_variant);
+        mark();
+    }
+    c->dn_ev_n = ev;
+    HIPCHK(c, hipGetLastError());
+    c->dn_done = true;
+    if (info) *info = {guided ? 1 : 0, render ? 1 : 0, dp.iterations, c->moments ? c->mom_frames : 0};
+    return PT_OK;
+}
+
+int pt_denoise(pt_ctx* c, const pt_denoise_params* params, pt_denoise_info* info) {
+    int rc = pt_denoise_async(c, params, info);
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+int pt_read_denoised_rgba32f(pt_ctx* c, float* dst, size_t bytes) {
+    if (!c || !dst) return PT_E_ARG;
+    if (!c->dn_done) return fail(c, PT_E_STATE, "no denoised image (pt_denoise first)");
+    const size_t need = (size_t)c->rows_local * c->cfg.width * sizeof(float4);
+    if (bytes < need) return fail(c, PT_E_ARG, "destination too small");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(dst, c->dn_out, need, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+int pt_read_denoised_rgba8_aces(pt_ctx* c, unsigned char* dst, size_t bytes) {
+    if (!c || !dst) return PT_E_ARG;
+    if (!c->dn_done) return fail(c, PT_E_STATE, "no denoised image (pt_denoise first)");
+    const long long n = (long long)c->rows_local * c->cfg.width;
+    if (bytes < (size_t)n * 4) return fail(c, PT_E_ARG, "destination too small");
+    if (n == 0) return PT_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (!c->dn_rgba8) HIPCHK(c, hipMalloc(&c->dn_rgba8, (size_t)n * sizeof(uchar4)));
+    // a view of its own: the image's (rgba8, stage_ok) is pt_present_*'s
+    hipLaunchKernelGGL(k_aces, dim3((unsigned)((n + 256 * kAcesPix - 1) / (256 * kAcesPix))), dim3(256), 0, c->stream,
+                       c->dn_out, c->dn_rgba8, n);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(dst, c->dn_rgba8, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+int pt_read_guides(pt_ctx* c, float* dst, size_t bytes) {
+    if (!c || !dst) return PT_E_ARG;
+    if (!c->guides_ok) return fail(c, PT_E_STATE, "no guides (pt_denoise first)");
+    const size_t n = (size_t)c->rows_local * c->cfg.width;
+    if (bytes < n * 8 * sizeof(float)) return fail(c, PT_E_ARG, "destination too small");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<float> g(n * 4);
+    for (int h = 0; h < 2; h++) {
+        if (n) HIPCHK(c, hipMemcpy(g.data(), c->dn_guide[h], n * sizeof(float4), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; i++) std::memcpy(dst + 8 * i + 4 * h, g.data() + 4 * i, 4 * sizeof(float));
+    }
+    return PT_OK;
+}
+
+// Measurements only (tools/denoise_measure.py; not part of the public ABI): how the iterations read their taps
+// (ptd::Variant), and events around the guide render, the prep and each iteration of the denoises that follow.
+int pt__denoise_debug(pt_ctx* c, int variant, int timing) {
+    if (!c || variant < 0 || variant > 1) return PT_E_ARG;
+    c->dn_variant = variant;
+    c->dn_timing = timing != 0;
+    c->dn_ev_n = 0;
+    return PT_OK;
+}
+// ms of the last timed denoise: out[0] guide render, [1] prep, [2 ..] the iterations; returns the count (waits).
+int pt__denoise_times(pt_ctx* c, float* out, int max_out) {
+    if (!c || !out) return PT_E_ARG;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int n = 0;
+    for (int i = 0; i + 1 < c->dn_ev_n && n < max_out; i++, n++) HIPCHK(c, hipEventElapsedTime(&out[n], c->dn_ev[i], c->dn_ev[i + 1]));
+    return n;
 }
 
 int pt_read_rgba8_aces(pt_ctx* c, unsigned char* dst, size_t bytes) {

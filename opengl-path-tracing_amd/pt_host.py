@@ -77,6 +77,29 @@ class AdaptiveStats(C.Structure):
                     pixel_frames=int(self.pixel_frames))
 
 
+class DenoiseParams(C.Structure):
+    """pt_denoise_params (include/pt_api.h)."""
+    _fields_ = [("iterations", C.c_int), ("guide_frames", C.c_int), ("sigma_lum", C.c_float),
+                ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float), ("sigma_depth", C.c_float)]
+
+
+class DenoiseInfo(C.Structure):
+    """pt_denoise_info (include/pt_api.h)."""
+    _fields_ = [(n, C.c_int) for n in ("guided", "guides_rendered", "iterations", "frames")]
+
+
+def denoise_params(**params):
+    """pt_denoise_defaults, with the given fields replaced."""
+    p = DenoiseParams()
+    lib().pt_denoise_defaults(C.byref(p))
+    names = [n for n, _ in DenoiseParams._fields_]
+    for key, value in params.items():
+        if key not in names:
+            raise TypeError("unknown denoise parameter %r (one of %s)" % (key, ", ".join(names)))
+        setattr(p, key, value)
+    return p
+
+
 _lib = None
 _F = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 _I = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
@@ -156,6 +179,13 @@ def lib():
             "pt_render_adaptive": (ip, [vp, ip, ip, ip, ip, fp, C.POINTER(ip), C.POINTER(AdaptiveStats)]),
             "pt_read_tile_frames": (ip, [vp, vp, ip, C.POINTER(ip), C.POINTER(ip)]),
             "pt_tile_retires_host": (ip, [_F, vp, C.c_size_t, ip, fp, C.POINTER(ip)]),
+            "pt_denoise_defaults": (None, [C.POINTER(DenoiseParams)]),
+            "pt_denoise": (ip, [vp, C.POINTER(DenoiseParams), C.POINTER(DenoiseInfo)]),
+            "pt_denoise_async": (ip, [vp, C.POINTER(DenoiseParams), C.POINTER(DenoiseInfo)]),
+            "pt_read_denoised_rgba32f": (ip, [vp, vp, C.c_size_t]),
+            "pt_read_denoised_rgba8_aces": (ip, [vp, vp, C.c_size_t]),
+            "pt_read_guides": (ip, [vp, vp, C.c_size_t]),
+            "pt_denoise_host": (ip, [_F, vp, _F, vp, ip, ip, C.POINTER(DenoiseParams), _F]),
             "pt_group_create": (ip, [C.POINTER(vp), ip, C.POINTER(vp)]),
             "pt_group_destroy": (None, [vp]),
             "pt_group_last_error": (C.c_char_p, [vp]),
@@ -572,6 +602,34 @@ class PathTracer:
         self._check(lib().pt_read_tile_frames(self.h, out.ctypes.data, len(out), C.byref(n), C.byref(tx)))
         return out[: n.value].reshape(-1, max(tx.value, 1))
 
+    def denoise(self, sync=True, **params):
+        """pt_denoise (sync=False: pt_denoise_async): the variance-guided a-trous filter of the image as
+        of the renders issued so far.  params: fields of pt_denoise_params over its
+        defaults.  -> dict(guided, guides_rendered, iterations, frames).  Never changes the image."""
+        p, info = denoise_params(**params), DenoiseInfo()
+        fn = lib().pt_denoise if sync else lib().pt_denoise_async
+        self._check(fn(self.h, C.byref(p), C.byref(info)))
+        return dict(guided=bool(info.guided), guides_rendered=bool(info.guides_rendered),
+                    iterations=int(info.iterations), frames=int(info.frames))
+
+    def read_denoised(self):
+        """The last denoise's (rows_local, W, 4) float32 result: rgb filtered, alpha the image's."""
+        out = np.zeros((self.rows_local, self.width, 4), np.float32)
+        self._check(lib().pt_read_denoised_rgba32f(self.h, out.ctypes.data, out.nbytes))
+        return out
+
+    def read_denoised_rgba8(self):
+        """... through the ACES view, (rows_local, W, 4) uint8."""
+        out = np.zeros((self.rows_local, self.width, 4), np.uint8)
+        self._check(lib().pt_read_denoised_rgba8_aces(self.h, out.ctypes.data, out.nbytes))
+        return out
+
+    def read_guides(self):
+        """The guides of the last denoise, (rows_local, W, 8) float32: N.rgb, Z, A.rgb, 0."""
+        out = np.zeros((self.rows_local, self.width, 8), np.float32)
+        self._check(lib().pt_read_guides(self.h, out.ctypes.data, out.nbytes))
+        return out
+
     def diag(self):
         """Lane utilisation per kernel phase from the last counting render."""
         v = np.zeros(16, np.uint64)
@@ -760,6 +818,37 @@ def noise_host(moments, frames, target, in_footprint=None):
     if rc:
         raise PTError(rc, "pt_noise_host: frames must be >= 2")
     return s.as_dict()
+
+
+def denoise_host(image, variance, guides, in_footprint=None, **params):
+    """pt_denoise_host: the denoising filter on the host (no device) -- the per-tap code is the
+    device kernel's own.  image (H, W, 4), variance (H, W) of the mean luminance's variance or None
+    (unguided), guides (H, W, 8) as PathTracer.read_guides, in_footprint (H, W) flags or None
+    -> (H, W, 4) float32."""
+    img = np.ascontiguousarray(image, np.float32)
+    if img.ndim != 3 or img.shape[2] != 4:
+        raise ValueError("image must be (H, W, 4)")
+    h, w = img.shape[:2]
+    g = np.ascontiguousarray(guides, np.float32)
+    if g.shape != (h, w, 8):
+        raise ValueError("guides must be (H, W, 8)")
+    var = None
+    if variance is not None:
+        var = np.ascontiguousarray(variance, np.float32)
+        if var.shape != (h, w):
+            raise ValueError("variance must be (H, W)")
+    fp = None
+    if in_footprint is not None:
+        fp = np.ascontiguousarray(np.asarray(in_footprint) != 0, np.uint8)
+        if fp.shape != (h, w):
+            raise ValueError("in_footprint must be (H, W)")
+    out = np.zeros((h, w, 4), np.float32)
+    p = denoise_params(**params)
+    rc = lib().pt_denoise_host(img.reshape(-1), None if var is None else var.ctypes.data, g.reshape(-1),
+                               None if fp is None else fp.ctypes.data, w, h, C.byref(p), out.reshape(-1))
+    if rc:
+        raise PTError(rc, "pt_denoise_host: iterations 1..8, guide_frames >= 1")
+    return out
 
 
 def tile_retires_host(moments, frames, target, in_footprint=None):
