@@ -49,6 +49,7 @@ using ptl::kPullBatch;
 
 // The device half, as sections of this translation unit (one compile, one set of kernel symbols):
 #include "pt_kparams.h"        // DevScene, KParams, Cnt, SceneView, the queue-head stride
+#include "pt_render_phase.h"   // what both render kernels run: the launch-uniform facts, the shared pieces of SHADE and LEAF
 #include "pt_render_sm.h"      // k_render_sm: scene access, the leaf tests, the three walks, the state machine
 #include "pt_render_pool.h"    // k_render_pool: the swept line with the path state in a per-wave LDS pool
 #include "pt_post_kernels.h"   // k_advance_frames, k_tile_order, k_accum_frames, k_aces, k_noise

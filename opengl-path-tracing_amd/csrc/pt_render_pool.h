@@ -6,10 +6,13 @@
 // its new state.  The order in which paths are served cannot show in the image: every frame's colour goes to the
 // frame-split scratch, and k_accum_frames applies the running mean in frame order.
 // No cross-wave communication: the only barrier follows the scene staging; list heads and counts are wave-uniform.
-// TWIN: the SHADE body (finish segment, queue pull, camera ray, segment set-up) and the swept LEAF body below restate
-// those of k_render_sm (pt_render_sm.h) with COMMON && SWEEP folded in, so that the existing kernels keep their device
-// code.  A change to the shading, the queue protocol or the leaf choice there must be made here too; only the bitwise
-// GPU tests (tests/test_gpu_path_pool.py: pool on against pool off against the oracle) catch drift between the two.
+// The arithmetic of the two phases is pt_render_phase.h's, the functions k_render_sm calls, with LaunchFacts<true, true>:
+// the finished segment, the queue reservation, the camera ray, the guard, the sphere's distance, the sweep candidates,
+// the leaf choice and the chain-order staging exist once.  What stays restated here, because it is bound to where the
+// path state lives: the decode of a queue id to a pixel (TWIN: k_render_sm's decode, pt_render_sm.h; this one packs
+// the pixel and the cost sample into the path record and has no tile shapes, raster order or clipped footprint), the
+// sphere's acceptance (one sphere, no loop or counter) and the skeleton of the swept LEAF body.
+// tests/test_gpu_path_pool.py compares the two kernels word for word.
 namespace {
 
 // The reference walk and leaf tests for a ray outside the exact-reciprocal guard (a few thousand of C2's segments),
@@ -34,11 +37,10 @@ __device__ __forceinline__ void pool_cold_walk(const KParams& p, const SceneView
         if (win_open(ta, t)) oka = tri_edges_at<true, false>(S, s0, mk(nda.x, nda.y, nda.z), o + d * ta, false, 0.0f, ca);
         if (win_closed(tb, t)) okb = tri_edges_at<true, false>(S, s0 + 1, mk(ndb.x, ndb.y, ndb.z), o + d * tb, false, 0.0f, cb);
         const float h1 = oka ? ta : -1.0f, h2 = okb ? tb : -1.0f;
-        const bool c1 = win_open(h1, t) & ((h1 < h2) | (h2 < 0.0001f));
-        const bool c2 = !c1 & win_open(h2, t);
-        if (c1 | c2) {
-            t = c1 ? h1 : h2;
-            hprim = s0 + (c1 ? 0 : 1);
+        const LeafChoice lc = leaf_choice(h1, h2, t);
+        if (lc.c1 | lc.c2) {
+            t = lc.c1 ? h1 : h2;
+            hprim = s0 + (lc.c1 ? 0 : 1);
         }
         w = b;
     }
@@ -56,16 +58,14 @@ template <int NT, int P, int MINW>
 __global__ __launch_bounds__(NT, MINW) void k_render_pool(KParams p) {
     static_assert(P >= 64 && P <= ptpool::kMaxPaths && P % 4 == 0, "one-byte list entries in a 16-byte padded array");
     using namespace ptpool;
+    const LaunchFacts<true, true> F{p};   // the shared pieces (pt_render_phase.h) see the COMMON && SWEEP line's constants
     const const_v4f* const sweep_tab = (const const_v4f*)(size_t)p.sweep_tab;
     resolve_frames(p);
     extern __shared__ float4 lds[];
     // staged: what swept rays read -- the triangle slots in chain order (planes), materials, the sphere, and the
     // leaf boxes for the exact re-test (the sweep table's own records: axis-paired, chain order)
     const int T = p.n_slots, nt = 4 * T, nm = 3 * p.n_mats, ns = 2, nb = 2 * p.n_sweep;
-    for (int i = threadIdx.x; i < nt; i += NT) {
-        const int slot = i >> 2, c = __float_as_int(p.sweep_tab[2 * (slot >> 1) + 1].w);
-        lds[(i & 3) * T + 2 * c + (slot & 1)] = p.sc.tris[i];
-    }
+    stage_tris_chain_order(lds, p, T, NT);
     for (int i = threadIdx.x; i < nm; i += NT) lds[nt + i] = p.sc.mats[i];
     for (int i = threadIdx.x; i < ns; i += NT) lds[nt + nm + i] = p.sc.spheres[i];
     for (int i = threadIdx.x; i < nb; i += NT) lds[nt + nm + ns + i] = p.sweep_tab[i];
@@ -126,45 +126,8 @@ __global__ __launch_bounds__(NT, MINW) void k_render_pool(KParams p) {
             if (on && !(t < 0.0f)) {   // a finished segment (t < 0: fresh)
                 const bool hit = hprim != -1;
                 pcost++;
-                bool finished = false;
-                f3 rgb = inc;
-                if (hit && pt::length_gt_001(col)) {
-                    const f3 hitp = o + d * t;
-                    f3 normal;
-                    int mat;
-                    if (hprim >= 0) {
-                        const float4 nq = tri_quad<true>(S, hprim, 0);
-                        normal = mk(nq.x, nq.y, nq.z);
-                        mat = __float_as_int(tri_quad<true>(S, hprim, 2).w);
-                    } else {
-                        const int si = -2 - hprim;
-                        float4 s0 = S.spheres[2 * si];
-                        normal = pt::normalize(hitp - mk(s0.x, s0.y, s0.z));
-                        mat = __float_as_int(S.spheres[2 * si + 1].x);
-                    }
-                    if (pt::dot(normal, d) > 0.0f) normal = normal * -1.0f;
-                    o = hitp;
-                    f3 diffuse = pt::normalize(normal + pt::random_unit_vector(state));
-                    float kk = 2.0f * pt::dot(normal, d);
-                    f3 specular = pt::normalize(d - normal * kk);
-                    float4 m0 = S.mats[3 * mat], m1 = S.mats[3 * mat + 1], m2 = S.mats[3 * mat + 2];
-                    float is_spec = (m1.w > pt::random01(state)) ? 1.0f : 0.0f;
-                    d = pt::mix(diffuse, specular, m0.w * is_spec);
-                    inc = inc + mk(m1.x, m1.y, m1.z) * col;
-                    col = col * pt::mix(mk(m0.x, m0.y, m0.z), mk(m2.x, m2.y, m2.z), is_spec);
-                    bounce++;
-                    if (bounce > p.max_bounce) {
-                        rgb = inc;
-                        finished = true;
-                    }
-                } else {
-                    f3 dir = pt::normalize(d);
-                    float tt = 0.5f * (dir.z + 1.0f);
-                    float omt = 1.0f - tt;
-                    f3 env = mk(omt * 1.0f + tt * 0.5f, omt * 1.0f + tt * 0.7f, omt * 1.0f + tt * 1.0f);
-                    rgb = inc + env * col;
-                    finished = true;
-                }
+                f3 rgb;
+                const bool finished = shade_segment<true>(F, p, S, hit, hprim, t, o, d, inc, col, state, bounce, rgb);
                 if (finished) {
                     bounce = -1;
                     const f3 px = (mk(0, 0, 0) + rgb) / 1.0f;
@@ -181,23 +144,9 @@ __global__ __launch_bounds__(NT, MINW) void k_render_pool(KParams p) {
             const bool want = on && xy == kNoItem;
             const unsigned long long m = __ballot(want);
             if (m) {
-                const unsigned need = (unsigned)__popcll(m);
-                const unsigned rank = (unsigned)rank_in(m);
-                const int leader = __ffsll((long long)m) - 1;
-                unsigned id;
-                if (qend - qnext >= need) {
-                    id = qnext + rank;
-                    qnext += need;
-                } else {
-                    const unsigned avail = qend - qnext;
-                    const unsigned take_ids = max(need - avail, (unsigned)p.pull_batch);
-                    unsigned base = 0;
-                    if (want && rank == 0u) base = atomicAdd(p.work_counter, take_ids);
-                    base = (unsigned)__builtin_amdgcn_readlane((int)base, leader);
-                    id = rank < avail ? qnext + rank : base + (rank - avail);
-                    qnext = base + (need - avail);
-                    qend = base + take_ids;
-                }
+                const QueueIds qi = queue_ids<true>(p, want, m, qnext, qend);
+                const unsigned id = qi.id;
+                qnext = qi.qnext, qend = qi.qend;
                 if (want) {
                     if (id >= total_ids) {
                         retired = true;      // the queue is empty: the path retires
@@ -223,48 +172,20 @@ __global__ __launch_bounds__(NT, MINW) void k_render_pool(KParams p) {
             }
             if (on && xy != kNoItem) {
                 const int lx = xy_lx(xy), y = p.row0 + xy_crow(xy) * p.row_stride;
-                if (bounce < 0) {    // camera ray due
-                    state = pt::seed(lx, y, p.frame_first + k);
-                    const float ax = pt::random01(state);
-                    const float ay = pt::random01(state);
-                    float u = pt::div_mk((float)lx + ax, p.fW, p.rW) - 0.5f;
-                    float v = pt::div_mk((float)y + ay, p.fH, p.rH) - 0.5f;
-                    d = pt::normalize((cfwd + cright * u) + cup * v);
-                    o = cpos;
-                    inc = mk(0, 0, 0);
-                    col = mk(1, 1, 1);
-                    bounce = 0;
-                }
-                const bool fast_seg =
-                       in_guard(o.x, 0x1p-40f, 0x1p60f) & in_guard(o.y, 0x1p-40f, 0x1p60f) &
-                       in_guard(o.z, 0x1p-40f, 0x1p60f) & in_range_abs(d.x, 0x1p-20f, 2.0f) &
-                       in_range_abs(d.y, 0x1p-20f, 2.0f) & in_range_abs(d.z, 0x1p-20f, 2.0f);
+                if (bounce < 0) camera_ray(F, p, cpos, cfwd, cright, cup, lx, y, k, 0, state, o, d, inc, col, bounce);
+                const bool fast_seg = seg_in_guard(F, o, d);
                 const f3 rd = fast_seg ? mk(pt::rcp_fast(d.x), pt::rcp_fast(d.y), pt::rcp_fast(d.z)) : mk(0, 0, 0);
                 t = __builtin_huge_valf();
                 hprim = -1;
                 {
-                    float4 s0 = S.spheres[0];
-                    f3 oc = o - mk(s0.x, s0.y, s0.z);
-                    float a = pt::dot(d, d);
-                    float half_b = pt::dot(oc, d);
-                    float cq = pt::dot(oc, oc) - s0.w;
-                    float disc = half_b * half_b - a * cq;
-                    float ht = disc < 0.0f ? -1.0f : (-half_b - pt::sqrt_g(disc)) / a;
+                    const float ht = sphere_t(S, 0, o, d);
                     if (win_open(ht, t)) {
                         t = ht;
                         hprim = -2;
                     }
                 }
                 const bool walk = !ray_has_nan(o, d);     // (a sweeping launch has nodes and triangles)
-                unsigned cand = 0u;
-                if (walk & fast_seg) {
-                    f3 ol, oh;
-                    ptc::cull_addends(o, rd, S.cm, S.ws, ol, oh);
-                    const ptc::SweepRay sr = ptc::sweep_ray(rd, ol, oh);
-                    bool in = true;
-                    if (p.sweep_root) in = ptc::sweep_root_hit(p.root_box, sr, t, S.clo);
-                    if (in) cand = ptc::sweep_mask(sr, t, S.clo, sweep_tab, p.n_sweep);
-                }
+                const unsigned cand = sweep_candidates(p, S, sweep_tab, walk & fast_seg, o, rd, t);
                 // rays outside the guard: cold code, the whole reference walk here (wave-uniform branch)
                 const bool cold = walk & !fast_seg;
                 if (__any(cold)) {
@@ -306,8 +227,8 @@ __global__ __launch_bounds__(NT, MINW) void k_render_pool(KParams p) {
             leaf_pair_tests<true, false>(S, at, s0, nd0, cop, o, d, t, p.compact_max, h1, h2, false, ca, cb);
             bool c1h = false, c2h = false;
             if (at) {
-                c1h = win_open(h1, t) & ((h1 < h2) | (h2 < 0.0001f));
-                c2h = !c1h & win_open(h2, t);
+                const LeafChoice lc = leaf_choice(h1, h2, t);
+                c1h = lc.c1, c2h = lc.c2;
             }
             // the sweep's test is conservative: the leaf's box passes the exact test at this t, or no triangle moves t
             const bool chk = at & (c1h | c2h);

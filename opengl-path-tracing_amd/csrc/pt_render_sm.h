@@ -1,8 +1,9 @@
 // pt_render_sm.h -- a section of the pt_render.hip translation unit, not a general-purpose header:
-// pt_render.hip includes it once, after pt_kparams.h.
+// pt_render.hip includes it once, after pt_render_phase.h.
 // The render kernel k_render_sm and what only it uses: the LDS / global access of the scene
-// (node_at, tri_quad, wrec_at), the lane utilities, the leaf phase's pair tests, the three walks
-// and the launch-uniform facts.  The per-ray arithmetic it calls is pt_isect.h.
+// (node_at, wrec_at), the lane utilities, the leaf phase's pair tests and the three walks.  The
+// per-ray arithmetic it calls is pt_isect.h; the launch-uniform facts, tri_quad and the pieces of
+// SHADE and LEAF it shares with k_render_pool are pt_render_phase.h.
 namespace {
 
 using pti::slab;
@@ -75,11 +76,6 @@ __device__ __forceinline__ void flush_counters(const KParams& p, const Cnt& c) {
 // there the loads, not the selects, set the pace, and the reference form measured faster.
 extern __shared__ float4 g_lds[];   // the state-machine kernel's scene copy (nodes first)
 // (scenes of at most kPadNodes nodes: images padded to that count, pt_launch_plan.h)
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) const v4f lds_v4f;
-// launch-constant data read through a wave-uniform index (the leaf sweep's table): in the constant address space
-// such reads are scalar loads, and the values arrive as scalar operands
-typedef __attribute__((address_space(4))) const v4f const_v4f;
 template <bool LDS, bool PADN = false>
 __device__ __forceinline__ void node_at(const SceneView& S, int i, float4& lo, float4& hi) {
     if (LDS) {      // i = byte offset from the LDS base, which is 0 (checked at kernel entry)
@@ -98,22 +94,6 @@ __device__ __forceinline__ void node_at(const SceneView& S, int i, float4& lo, f
         hi = S.nodes[2 * i + 1];
     }
 }
-
-template <bool LDS>
-__device__ __forceinline__ float4 tri_quad(const SceneView& S, int slot, int k) {
-#ifdef PT_DIAG_TRIS_GLOBAL   // diagnostic build (LDS bank-conflict attribution): triangles from HBM
-    return S.tris[4 * slot + k];
-#else
-    return LDS ? S.tris[slot + k * S.tp] : S.tris[4 * slot + k];
-#endif
-}
-
-// in_guard / in_range_abs: pt_math.h (one unsigned window on the bit patterns)
-using pt::in_guard;
-using pt::in_range_abs;
-
-using pt::win_open;    // the hit windows 1e-4 < x < t and 1e-4 <= x < t (pt_math.h)
-using pt::win_closed;
 
 // The three edge tests (:299-306) of triangle `slot` at p with normal n: the caller has n
 // from the plane test (quad 0), so only the vertices (quads 1-3) are read.
@@ -139,10 +119,6 @@ __device__ __forceinline__ int lane_id() {
     int l;
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
     return l;
-}
-// Number of set bits of m below this lane.
-__device__ __forceinline__ int rank_in(unsigned long long m) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
 }
 __device__ __forceinline__ float fperm_f(int dst_bytes, float v) {
     return __int_as_float(__builtin_amdgcn_ds_permute(dst_bytes, __float_as_int(v)));
@@ -253,9 +229,9 @@ __device__ __forceinline__ void leaf_pair_tests(const SceneView& S, bool at, int
 // With the leaf sweep (scenes of a few leaves, pt_cull.h) a ray inside the guard never enters
 // TRAV: its segment set-up leaves the candidate leaves as a bit mask in bi, and the lane stays
 // in LEAF until the mask is empty.
-// TWIN: k_render_pool (pt_render_pool.h) restates the SHADE body and the swept LEAF body of the COMMON && SWEEP line
-// on path state held in LDS.  A change to the shading, the queue protocol or the leaf choice here must be made there
-// too; tests/test_gpu_path_pool.py compares the two kernels word for word.
+// The pieces of SHADE and LEAF that do not depend on where the path state lives are pt_render_phase.h's, shared with
+// k_render_pool (pt_render_pool.h), which runs the COMMON && SWEEP line on path state held in LDS.
+// TWIN: the decode of a queue id to a pixel below is restated there in the pool record's packing.
 // =====================================================================================
 enum : int { ST_DONE = 0, ST_TRAV = 1, ST_LEAF = 2, ST_SHADE = 3 };
 #ifndef PT_WALK_UNROLL
@@ -481,34 +457,6 @@ constexpr int kWaveTraceMax = 16384;
 __device__ unsigned long long g_wave_trace[kWaveTraceMax * 4];
 #endif
 
-// The launch-uniform facts the state machine branches on.  The generic kernels read them from
-// their arguments, on every trip round the loop; a COMMON instantiation holds the default
-// configuration's as constants (ptl::common_launch and enqueue_render vouch for each), so the
-// untaken sides -- display modes 2-4, Moller-Trumbore, the non-culling walks, the raster tile
-// order, the item division -- are not in its code.  Uniform control flow and address arithmetic
-// only: every lane runs the same operations on the same values either way.  Measured on C2
-// (DESIGN.md §5.2): mode, flags and the culling walk give about 1.8% each, the tile facts 0.3%,
-// the single sphere nothing in time (7 fewer spilled SGPRs); the thresholds and the walk floor
-// are not here because as constants they cost 1.1%.
-// The leaf sweep (pt_cull.h, DESIGN.md §5.6, "The leaf sweep") is such a fact too: the COMMON line is built with it on and with it
-// off (SWEEP), so tuning key 23 compares the two walks of one kernel; a generic line reads the kernel argument.
-template <bool COMMON, bool SWEEP = false>
-struct LaunchFacts {
-    const KParams& p;
-    __device__ __forceinline__ bool sweep() const { return COMMON ? SWEEP : p.sweep != 0; }
-    __device__ __forceinline__ int mode() const { return COMMON ? 1 : p.mode; }
-    __device__ __forceinline__ int flags() const { return COMMON ? 0 : p.flags; }
-    __device__ __forceinline__ bool cons_walk() const { return COMMON || p.cons_walk != 0; }
-    __device__ __forceinline__ bool scene_fast() const { return COMMON || p.scene_fast != 0; }
-    __device__ __forceinline__ float win_lo() const { return COMMON ? ptc::kWindowLo : p.win_lo; }
-    __device__ __forceinline__ int n_spheres() const { return COMMON ? 1 : p.sc.n_spheres; }
-    __device__ __forceinline__ int tile_shift() const { return COMMON ? 0 : p.tile_shift; }
-    __device__ __forceinline__ bool tile_perm() const { return COMMON || p.tile_perm != nullptr; }
-    __device__ __forceinline__ bool tile_cost() const { return COMMON || p.tile_cost != nullptr; }
-    // COMMON: the footprint is the image (x_limit >= W; a local row's y is below y_limit)
-    __device__ __forceinline__ bool inside(int cx, int cy) const { return COMMON || ((cx < p.x_limit) & (cy < p.y_limit)); }
-};
-
 template <bool COUNT, bool LDS, int MINW, bool MULTI, bool SPLIT, bool PADN = false, int NT = 256, bool WIDE = false,
           bool COMMON = false, bool SWEEP = false>
 __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
@@ -541,13 +489,7 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
         const int nm = 3 * p.n_mats, ns = 2 * F.n_spheres();
         for (int i = threadIdx.x; i < nn; i += blockDim.x) lds[i] = wsrc[i];   // ready-made image
         if (sweep) {
-            // the leaf sweep numbers the leaves by their chain position (a candidate bit is one), so this copy holds
-            // leaf pair q's two slots at 2 c, 2 c + 1, c = the chain position of pair q (the table's inverse map):
-            // every slot index the kernel keeps (s0, hprim) then is one of this copy
-            for (int i = threadIdx.x; i < nt; i += blockDim.x) {
-                const int slot = i >> 2, c = __float_as_int(p.sweep_tab[2 * (slot >> 1) + 1].w);
-                lds[nn + (i & 3) * T + 2 * c + (slot & 1)] = p.sc.tris[i];
-            }
+            stage_tris_chain_order(lds + nn, p, T, blockDim.x);
         } else {
             for (int i = threadIdx.x; i < nt; i += blockDim.x) lds[nn + (i & 3) * T + (i >> 2)] = p.sc.tris[i];
         }
@@ -686,64 +628,8 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
                 const bool hit = hprim != -1;
                 if (COUNT) { c.seg++; if (hit) c.hits++; diag_tick(c.sw, c.sl); }
                 pcost++;
-                bool finished = false;
-                f3 rgb = inc;
-                if (hit && pt::length_gt_001(col)) {
-                    const f3 hitp = o + d * t;
-                    f3 normal;
-                    int mat;
-                    if (hprim >= 0) {             // triangle: stored n, flipped (:421-428)
-                        const float4 nq = tri_quad<LDS>(S, hprim, 0);
-                        normal = mk(nq.x, nq.y, nq.z);
-                        mat = __float_as_int(tri_quad<LDS>(S, hprim, 2).w);
-                    } else {                      // sphere: normalize(hit - center) (:380)
-                        const int si = -2 - hprim;
-                        float4 s0 = S.spheres[2 * si];
-                        normal = pt::normalize(hitp - mk(s0.x, s0.y, s0.z));
-                        mat = __float_as_int(S.spheres[2 * si + 1].x);
-                    }
-                    if (pt::dot(normal, d) > 0.0f) normal = normal * -1.0f;
-                    if (F.mode() == 2) {
-                        rgb = (normal + mk(1, 1, 1)) * 0.5f;
-                        finished = true;
-                    } else if (F.mode() == 4) {
-                        float s = pt::length(hitp - o);
-                        float dist = 1.0f - pt::fsqrt(s + 1.0f) / (s + 1.0f);
-                        float q = dist * dist;
-                        rgb = mk(q, q, q);
-                        finished = true;
-                    } else {
-                        o = hitp;
-                        f3 diffuse = pt::normalize(normal + pt::random_unit_vector(state));
-                        float kk = 2.0f * pt::dot(normal, d);
-                        f3 specular = pt::normalize(d - normal * kk);
-                        float4 m0 = S.mats[3 * mat], m1 = S.mats[3 * mat + 1], m2 = S.mats[3 * mat + 2];
-                        if (F.mode() == 3) {
-                            rgb = mk(m0.x, m0.y, m0.z);
-                            finished = true;
-                        } else {
-                            float is_spec = (m1.w > pt::random01(state)) ? 1.0f : 0.0f;
-                            d = pt::mix(diffuse, specular, m0.w * is_spec);
-                            inc = inc + mk(m1.x, m1.y, m1.z) * col;
-                            col = col * pt::mix(mk(m0.x, m0.y, m0.z), mk(m2.x, m2.y, m2.z), is_spec);
-                            bounce++;
-                            if (bounce > p.max_bounce) {
-                                rgb = inc;
-                                finished = true;
-                            }
-                        }
-                    }
-                } else {
-                    f3 env = mk(0, 0, 0);
-                    if (!(F.flags() & PT_FLAG_NO_SKY)) {
-                        f3 dir = pt::normalize(d);
-                        float tt = 0.5f * (dir.z + 1.0f);
-                        float omt = 1.0f - tt;
-                        env = mk(omt * 1.0f + tt * 0.5f, omt * 1.0f + tt * 0.7f, omt * 1.0f + tt * 1.0f);
-                    }
-                    rgb = inc + env * col;
-                    finished = true;
-                }
+                f3 rgb;
+                const bool finished = shade_segment<LDS>(F, p, S, hit, hprim, t, o, d, inc, col, state, bounce, rgb);
                 if (finished) bounce = -1;
                 if (finished) {
                     bool frame_done = true;
@@ -779,33 +665,13 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
                 if (F.tile_cost() && tile_id != ~0u) atomicAdd(&p.tile_cost[tile_id], pcost);
                 lx = -1;
             }
-            // wave-aggregated pull from the work queue.  Frame-split items are short, so
-            // there a wave reserves ids in batches of pull_batch (one queue atomic per batch
-            // instead of per pull; the counter is one address for the whole chip).  (A queue
-            // sharded over 8 heads, one per XCD, measured slower on one-frame launches with
-            // and without overlap, and cost 5% on C2 in the same kernel.)
+            // wave-aggregated pull from the work queue (queue_ids, pt_render_phase.h)
             bool want = st == ST_SHADE && lx < 0;
             unsigned long long m = __ballot(want);
             if (m) {
-                const unsigned need = (unsigned)__popcll(m);
-                const unsigned rank = (unsigned)rank_in(m);
-                const int leader = __ffsll((long long)m) - 1;
-                unsigned id;
-                if (SPLIT && qend - qnext >= need) {
-                    id = qnext + rank;
-                    qnext += need;
-                } else {
-                    const unsigned avail = SPLIT ? qend - qnext : 0u;
-                    const unsigned take = SPLIT ? max(need - avail, (unsigned)p.pull_batch) : need;
-                    unsigned base = 0;
-                    if (want && rank == 0u) base = atomicAdd(p.work_counter, take);   // the leader
-                    base = (unsigned)__builtin_amdgcn_readlane((int)base, leader);
-                    id = rank < avail ? qnext + rank : base + (rank - avail);
-                    if (SPLIT) {
-                        qnext = base + (need - avail);
-                        qend = base + take;
-                    }
-                }
+                const QueueIds qi = queue_ids<SPLIT>(p, want, m, qnext, qend);
+                const unsigned id = qi.id;
+                qnext = qi.qnext, qend = qi.qend;
                 if (want) {
                     if (id >= total_ids) {
                         st = ST_DONE;
@@ -852,32 +718,9 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
                 }
             }
             if (st == ST_SHADE && lx >= 0) {
-                if (bounce < 0) {    // camera ray due (:514-542)
-                    if (r == 0) state = pt::seed(lx, y, p.frame_first + k);
-                    float ax = 0.0f, ay = 0.0f;
-                    if (!(F.flags() & PT_FLAG_NO_AA)) {
-                        ax = pt::random01(state);
-                        ay = pt::random01(state);
-                    }
-                    // (x + jitter) / W by the exact reciprocal RN(1/W) and a Markstein
-                    // correction: the numerator is 0 or in [2^-32, 2^17), W <= 2^16, so the
-                    // remainder is exact and the quotient correctly rounded (test_exact_div)
-                    float u = pt::div_mk((float)lx + ax, p.fW, p.rW) - 0.5f;
-                    float v = pt::div_mk((float)y + ay, p.fH, p.rH) - 0.5f;
-                    d = pt::normalize((cfwd + cright * u) + cup * v);
-                    o = cpos;
-                    inc = mk(0, 0, 0);
-                    col = mk(1, 1, 1);
-                    bounce = 0;
-                }
+                if (bounce < 0) camera_ray(F, p, cpos, cfwd, cright, cup, lx, y, k, r, state, o, d, inc, col, bounce);   // (:514-542)
                 // segment set-up: exact-reciprocal guard, spheres (:372-385), walk start
-                // the ray half of the guard, evaluated without short-circuit branches (each
-                // && of the old form was an exec-mask branch): every origin component 0 or
-                // in [2^-40, 2^60], every direction component in [2^-20, 2] (NaN fails)
-                const bool fast_seg =
-                       F.scene_fast() & in_guard(o.x, 0x1p-40f, 0x1p60f) & in_guard(o.y, 0x1p-40f, 0x1p60f) &
-                       in_guard(o.z, 0x1p-40f, 0x1p60f) & in_range_abs(d.x, 0x1p-20f, 2.0f) &
-                       in_range_abs(d.y, 0x1p-20f, 2.0f) & in_range_abs(d.z, 0x1p-20f, 2.0f);
+                const bool fast_seg = seg_in_guard(F, o, d);
                 // under the guard |d_i| is in [2^-20, 2]: rcp_fast is the exact RN(1/d_i); rd = 0
                 // marks a segment outside it
                 rd = fast_seg ? mk(pt::rcp_fast(d.x), pt::rcp_fast(d.y), pt::rcp_fast(d.z)) : mk(0, 0, 0);
@@ -887,15 +730,7 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
                 hprim = -1;
                 if (!(F.flags() & PT_FLAG_NO_SPHERES)) {
                     for (int si = 0; si < F.n_spheres(); si++) {
-                        float4 s0 = S.spheres[2 * si];
-                        f3 oc = o - mk(s0.x, s0.y, s0.z);
-                        float a = pt::dot(d, d);
-                        float half_b = pt::dot(oc, d);
-                        float cq = pt::dot(oc, oc) - s0.w;
-                        float disc = half_b * half_b - a * cq;
-                        // the IEEE division sequence, not div_g: its range guard's four compares
-                        // cost more than the sequence (same quotient; +0.6% on C2, round 5)
-                        float ht = disc < 0.0f ? -1.0f : (-half_b - pt::sqrt_g(disc)) / a;
+                        const float ht = sphere_t(S, si, o, d);
                         if (COUNT) c.sph++;
                         if (win_open(ht, t)) {
                             t = ht;
@@ -921,17 +756,7 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
                     // the leaf sweep: a ray inside the guard tests every leaf box once at this t and never walks;
                     // bi carries its candidate leaves, lowest bit first (the root-inside test, the octant image and
                     // the walk start above are only for the rays outside the guard, which walk from the root)
-                    unsigned cand = 0u;
-                    if (walk & fast_seg) {
-                        f3 ol, oh;
-                        ptc::cull_addends(o, rd, S.cm, S.ws, ol, oh);
-                        const ptc::SweepRay sr = ptc::sweep_ray(rd, ol, oh);
-                        // a camera outside the root box (wave-uniform): many of its rays miss the scene, and a wave
-                        // of them skips the sweep on the root's own test
-                        bool in = true;
-                        if (p.sweep_root) in = ptc::sweep_root_hit(p.root_box, sr, t, S.clo);
-                        if (in) cand = ptc::sweep_mask(sr, t, S.clo, sweep_tab, p.n_sweep);
-                    }
+                    const unsigned cand = sweep_candidates(p, S, sweep_tab, walk & fast_seg, o, rd, t);
                     bi = walk ? (fast_seg ? (int)cand : 0) : -1;
                     st = walk ? (fast_seg ? (cand ? ST_LEAF : ST_SHADE) : ST_TRAV) : ST_SHADE;
                 }
@@ -982,8 +807,8 @@ __global__ __launch_bounds__(NT, MINW) void k_render_sm(KParams p) {
             }
             bool c1 = false, c2 = false;
             if (at) {
-                c1 = win_open(h1, t) & ((h1 < h2) | (h2 < 0.0001f));
-                c2 = !c1 & win_open(h2, t);
+                const LeafChoice lc = leaf_choice(h1, h2, t);
+                c1 = lc.c1, c2 = lc.c2;
             }
             if (LDS && !COUNT && F.cons_walk()) {
                 // the culling walk stopped here on the conservative test: the reference tests
