@@ -252,8 +252,10 @@ PT_HD unsigned sweep_push(unsigned m, bool hit) {
 // pti::slab_fast reads: k_render_pool stages these records for its exact leaf re-test), and its triangle-pair index;
 // `inverse` of entry p is the chain position of pair p (both render kernels stage the triangle slots by it).
 // The boxes run from the last to the first so that a set bit enters as the carry of mask + mask.
-// (Requesting box k - 1's bounds before box k's test measured 0.5% slower on C2 than this plain loop: the other
-// resident waves already cover the scalar loads' latency.)
+// (This plain loop requests one box's bounds and waits for all of them before the box's 18 VALU.  In k_render_sm, at
+// seven waves per SIMD, the other resident waves cover that latency: requesting box k - 1's bounds before box k's
+// test measured 0.5% slower on C2 there.  At the path pool's four waves per SIMD they do not: k_render_pool runs
+// sweep_mask_piped below on its LDS copy of the table, +5% on C2; DESIGN.md §5.12, "Round 16".)
 template <class T>
 PT_HD unsigned sweep_mask(const SweepRay& r, float t0, float c_lo, T table, int n) {
     unsigned m = 0u;
@@ -262,6 +264,67 @@ PT_HD unsigned sweep_mask(const SweepRay& r, float t0, float c_lo, T table, int 
         m = sweep_push(m, sweep_hit(a.x, a.y, a.z, a.w, b.x, b.y, r, t0, c_lo));
     }
     return m;
+}
+// The same mask with the bounds of D boxes in flight: the n mod D highest boxes go first, plainly, then whole
+// chunks of D boxes, the next chunk's bounds requested before the current chunk is tested (and none past the last:
+// no read below the table).  Per box the same sweep_hit and sweep_push on the same values in the same order as
+// sweep_mask, so the masks are equal; only when a load is issued differs.  Two register sets take the chunks in
+// turn (a single rotating set cost the device 13 register copies per two boxes), and reads that return in order
+// (LDS) are awaited by count.
+#if defined(__clang__)
+#define PT_SWEEP_UNROLL _Pragma("unroll")
+#else
+#define PT_SWEEP_UNROLL
+#endif
+// (The compiler's scheduler works block by block: a load whose first use is in the next trip round the loop looks free
+// to it and goes to the end of the block, where it is awaited at once.  The fence keeps the request where it is written.)
+PT_HD void sweep_issue_fence() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_sched_barrier(0);
+#endif
+}
+template <int D> struct SweepChunk { float q[D][6]; };      // boxes k, k - 1, .. k - D + 1, box k - j in q[j]
+template <int D, class T>
+PT_HD void sweep_chunk_load(SweepChunk<D>& c, T table, int k) {
+    PT_SWEEP_UNROLL
+    for (int j = 0; j < D; j++) {
+        const auto a = table[2 * (k - j)], b = table[2 * (k - j) + 1];
+        c.q[j][0] = a.x, c.q[j][1] = a.y, c.q[j][2] = a.z, c.q[j][3] = a.w, c.q[j][4] = b.x, c.q[j][5] = b.y;
+    }
+}
+template <int D>
+PT_HD unsigned sweep_chunk_test(unsigned m, const SweepChunk<D>& c, const SweepRay& r, float t0, float c_lo) {
+    PT_SWEEP_UNROLL
+    for (int j = 0; j < D; j++)
+        m = sweep_push(m, sweep_hit(c.q[j][0], c.q[j][1], c.q[j][2], c.q[j][3], c.q[j][4], c.q[j][5], r, t0, c_lo));
+    return m;
+}
+template <int D, class T>
+PT_HD unsigned sweep_mask_piped(const SweepRay& r, float t0, float c_lo, T table, int n) {
+    static_assert(D >= 1 && D <= 8, "boxes in flight");
+    unsigned m = 0u;
+    int k = n - 1;
+    for (int j = n % D; j > 0; j--, k--) {
+        const auto a = table[2 * k], b = table[2 * k + 1];
+        m = sweep_push(m, sweep_hit(a.x, a.y, a.z, a.w, b.x, b.y, r, t0, c_lo));
+    }
+    if (k < 0) return m;
+    SweepChunk<D> ca, cb;       // k + 1 is a multiple of D: whole chunks from here, the one at k in ca
+    sweep_chunk_load(ca, table, k);
+    for (; k >= 3 * D - 1; k -= 2 * D) {    // two more chunks below
+        sweep_chunk_load(cb, table, k - D);
+        sweep_issue_fence();
+        m = sweep_chunk_test(m, ca, r, t0, c_lo);
+        sweep_chunk_load(ca, table, k - 2 * D);
+        sweep_issue_fence();
+        m = sweep_chunk_test(m, cb, r, t0, c_lo);
+    }
+    if (k >= 2 * D - 1) {                   // one more
+        sweep_chunk_load(cb, table, k - D);
+        m = sweep_chunk_test(m, ca, r, t0, c_lo);
+        return sweep_chunk_test(m, cb, r, t0, c_lo);
+    }
+    return sweep_chunk_test(m, ca, r, t0, c_lo);
 }
 template <class T>
 PT_HD unsigned sweep_mask(pt::f3 rd, pt::f3 ol, pt::f3 oh, float t0, float c_lo, T table, int n) {

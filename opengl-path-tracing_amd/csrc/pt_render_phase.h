@@ -219,7 +219,11 @@ __device__ __forceinline__ float sphere_t(const SceneView& S, int si, f3 o, f3 d
 }
 
 // The leaf sweep of a new segment inside the guard (`on`): its candidate leaves at this t, lowest bit first.
-__device__ __forceinline__ unsigned sweep_candidates(const KParams& p, const SceneView& S, const const_v4f* sweep_tab,
+// DEPTH 0: the plain loop (ptc::sweep_mask), one box's bounds requested and awaited per iteration; DEPTH > 0: the
+// pipelined loop (ptc::sweep_mask_piped) with DEPTH boxes' bounds in flight.  `table` is the sweep table through a
+// wave-uniform index: the constant-address-space view (scalar loads) or the workgroup's LDS copy (broadcast reads).
+template <int DEPTH = 0, class Table>
+__device__ __forceinline__ unsigned sweep_candidates(const KParams& p, const SceneView& S, Table table,
                                                      bool on, f3 o, f3 rd, float t) {
     unsigned cand = 0u;
     if (on) {
@@ -230,7 +234,8 @@ __device__ __forceinline__ unsigned sweep_candidates(const KParams& p, const Sce
         // of them skips the sweep on the root's own test
         bool in = true;
         if (p.sweep_root) in = ptc::sweep_root_hit(p.root_box, sr, t, S.clo);
-        if (in) cand = ptc::sweep_mask(sr, t, S.clo, sweep_tab, p.n_sweep);
+        if (in) cand = DEPTH > 0 ? ptc::sweep_mask_piped<(DEPTH > 0 ? DEPTH : 1)>(sr, t, S.clo, table, p.n_sweep)
+                                 : ptc::sweep_mask(sr, t, S.clo, table, p.n_sweep);
     }
     return cand;
 }

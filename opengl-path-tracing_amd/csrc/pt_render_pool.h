@@ -13,6 +13,26 @@
 // the pixel and the cost sample into the path record and has no tile shapes, raster order or clipped footprint), the
 // sphere's acceptance (one sphere, no loop or counter) and the skeleton of the swept LEAF body.
 // tests/test_gpu_path_pool.py compares the two kernels word for word.
+// The leaf sweep of the set-up pass keeps bounds in flight ("Round 16"): at four waves per SIMD the
+// plain loop's scalar load and full wait per box stood exposed 18 times per set-up pass on Cornell.  Two build
+// switches, so that each form can be compared against the plain one in one process (tools/ab_inproc.py):
+//   PT_POOL_SWEEP_DEPTH  boxes per chunk of the pipelined sweep (ptc::sweep_mask_piped: one chunk's bounds are
+//                        requested while the other chunk is tested); 0: ptc::sweep_mask, as k_render_sm runs it
+//   PT_POOL_SWEEP_LDS    1: the bounds come from the workgroup's LDS copy of the table (the one staged for the exact
+//                        re-test) by broadcast reads, which return in order and are awaited by count; 0: from the
+//                        scalar cache, whose loads return out of order and are awaited all together
+// Same-process A/B on C2's 1024-frame launch against the plain loop, whose copy measured ±0.1-0.5% in those visits
+// (profiles/ab/r16_pool_waits/):
+//   LDS, depth 1 / 2 / 3 / 4:  +4.6% / +4.8..5.6% / +5.0% / +4.7%
+//   scalar cache, depth 2:     -0.3%  (the second set of bounds costs 24 SGPRs in a kernel that is out of them: 46
+//                                      lane writes and 61 lane reads of spilled SGPRs in the code, against 19 and 32)
+// Depth 2 ships: 87 VGPRs (81 with the plain loop; 128 keep four waves per SIMD); depth 3 is within the floor of it.
+#ifndef PT_POOL_SWEEP_DEPTH
+#define PT_POOL_SWEEP_DEPTH 2
+#endif
+#ifndef PT_POOL_SWEEP_LDS
+#define PT_POOL_SWEEP_LDS 1
+#endif
 namespace {
 
 // The reference walk and leaf tests for a ray outside the exact-reciprocal guard (a few thousand of C2's segments),
@@ -60,6 +80,7 @@ __global__ __launch_bounds__(NT, MINW) void k_render_pool(KParams p) {
     using namespace ptpool;
     const LaunchFacts<true, true> F{p};   // the shared pieces (pt_render_phase.h) see the COMMON && SWEEP line's constants
     const const_v4f* const sweep_tab = (const const_v4f*)(size_t)p.sweep_tab;
+    (void)sweep_tab;    // (the LDS form of the sweep reads the staged copy)
     resolve_frames(p);
     extern __shared__ float4 lds[];
     // staged: what swept rays read -- the triangle slots in chain order (planes), materials, the sphere, and the
@@ -185,7 +206,11 @@ __global__ __launch_bounds__(NT, MINW) void k_render_pool(KParams p) {
                     }
                 }
                 const bool walk = !ray_has_nan(o, d);     // (a sweeping launch has nodes and triangles)
-                const unsigned cand = sweep_candidates(p, S, sweep_tab, walk & fast_seg, o, rd, t);
+#if PT_POOL_SWEEP_DEPTH > 0 && PT_POOL_SWEEP_LDS
+                const unsigned cand = sweep_candidates<PT_POOL_SWEEP_DEPTH>(p, S, boxes, walk & fast_seg, o, rd, t);
+#else
+                const unsigned cand = sweep_candidates<PT_POOL_SWEEP_DEPTH>(p, S, sweep_tab, walk & fast_seg, o, rd, t);
+#endif
                 // rays outside the guard: cold code, the whole reference walk here (wave-uniform branch)
                 const bool cold = walk & !fast_seg;
                 if (__any(cold)) {
