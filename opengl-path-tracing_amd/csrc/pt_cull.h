@@ -255,7 +255,8 @@ PT_HD unsigned sweep_push(unsigned m, bool hit) {
 // (This plain loop requests one box's bounds and waits for all of them before the box's 18 VALU.  In k_render_sm, at
 // seven waves per SIMD, the other resident waves cover that latency: requesting box k - 1's bounds before box k's
 // test measured 0.5% slower on C2 there.  At the path pool's four waves per SIMD they do not: k_render_pool runs
-// sweep_mask_piped below on its LDS copy of the table, +5% on C2; DESIGN.md §5.12, "Round 16".)
+// sweep_mask_piped below on its LDS copy of the table, +5% on C2; DESIGN.md §5.12, "Round 16" -- and since round 17
+// sweep_mask_signed_piped, further below, on the signed table: 6 of the 12 fmas, +4% more.)
 template <class T>
 PT_HD unsigned sweep_mask(const SweepRay& r, float t0, float c_lo, T table, int n) {
     unsigned m = 0u;
@@ -329,6 +330,87 @@ PT_HD unsigned sweep_mask_piped(const SweepRay& r, float t0, float c_lo, T table
 template <class T>
 PT_HD unsigned sweep_mask(pt::f3 rd, pt::f3 ol, pt::f3 oh, float t0, float c_lo, T table, int n) {
     return sweep_mask(sweep_ray(rd, ol, oh), t0, c_lo, table, n);
+}
+// ------------------------------------------------------------------ the signed sweep table ("Round 17")
+// Where a read can carry a per-lane address (k_render_pool's LDS copy of the table), the choice between a box's two
+// bounds is made by the address and costs nothing: per leaf the signed table holds 3 quads = six 8-byte pairs,
+//   byte 16 a     : {lo_a, hi_a}   near first for rd_a > 0
+//   byte 16 a + 8 : {hi_a, lo_a}   near first otherwise
+// for the axes a = x, y, z, and a lane reads axis a of box k as one pair at pair index 6 k + 2 a + s_a with
+// s_a = !(rd_a > 0), sweep_ray's predicate.  Two lanes of a read either share an address (a broadcast) or differ by
+// 8 bytes within one quad, which are different banks: no conflict.  The pair is cull_hit's (near, far) of the ray's
+// octant image, so the test is cull_hit itself, 6 fmas where sweep_hit runs 12:
+//   near_a = fma(n_a, rd_a, ol_a),   far_a = fma(f_a, rd_a, oh_a).
+// It equals sweep_hit on the same box.  For rd_a > 0 sweep_hit's inner fmas are fma(hi_a, 0, ol_a) and
+// fma(lo_a, 0, oh_a): a finite bound times zero is a zero, so they return ol_a and oh_a -- exactly, except that an
+// addend -0 may come back as +0 -- and the outer ones are fma(lo_a, rd_a, ol_a) and fma(hi_a, rd_a, oh_a), the two
+// above with (n, f) = (lo, hi).  Otherwise rp_a = 0: the inner fmas are fma(hi_a, rd_a, ol_a) and fma(lo_a, rd_a, oh_a),
+// the two above with (n, f) = (hi, lo), and the outer ones add a zero to them, which again changes at most the sign
+// of a zero result.  A zero of either sign orders alike in fmaxf, fminf, min_t and <=, and no NaN arises on either
+// side (finite bounds and reciprocals, finite addends), so the verdicts are equal: (c) of the sweep's argument above
+// stands, now with cull_hit in person.
+constexpr int kSignedQuads = 3;                     // per leaf
+constexpr int kSignedPairs = 2 * kSignedQuads;      // 8-byte pairs per leaf
+// Quad `axis` of a leaf's signed record from its two sweep-table quads a = {lo.x, hi.x, lo.y, hi.y}, b = {lo.z, hi.z, ..}.
+template <class Q>
+PT_HD void sweep_signed_quad(const Q& a, const Q& b, int axis, float q[4]) {
+    const float lo = axis == 0 ? a.x : (axis == 1 ? a.z : b.x), hi = axis == 0 ? a.y : (axis == 1 ? a.w : b.y);
+    q[0] = lo, q[1] = hi, q[2] = hi, q[3] = lo;
+}
+// The pair index of a ray's read on `axis` within a leaf's record (add kSignedPairs per leaf).
+PT_HD int sweep_signed_pair(float rd_axis, int axis) { return 2 * axis + (rd_axis > 0.0f ? 0 : 1); }
+// One box from its three pairs (near, far per axis) at t0.
+PT_HD bool sweep_hit_signed(float xn, float xf, float yn, float yf, float zn, float zf, pt::f3 rd, pt::f3 ol, pt::f3 oh,
+                            float t0, float c_lo) {
+    return cull_hit(xn, xf, yn, yf, zn, zf, rd, ol, oh, t0, c_lo);
+}
+// The candidate mask from the signed table, with the chunk structure of sweep_mask_piped: the n mod D highest boxes
+// first, then whole chunks of D boxes from two register sets, the next chunk's pairs requested before the current
+// chunk is tested, none below the table.  px, py, pz: the lane's three views of the table, indexable in pairs
+// (.x = near, .y = far), already offset by sweep_signed_pair, so box k's pairs are px[6 k], py[6 k], pz[6 k]: on the
+// device three address registers per segment and immediate offsets in the loop.
+template <int D, class P>
+PT_HD void sweep_signed_load(SweepChunk<D>& c, P px, P py, P pz, int k) {
+    PT_SWEEP_UNROLL
+    for (int j = 0; j < D; j++) {
+        const auto x = px[kSignedPairs * (k - j)], y = py[kSignedPairs * (k - j)], z = pz[kSignedPairs * (k - j)];
+        c.q[j][0] = x.x, c.q[j][1] = x.y, c.q[j][2] = y.x, c.q[j][3] = y.y, c.q[j][4] = z.x, c.q[j][5] = z.y;
+    }
+}
+template <int D>
+PT_HD unsigned sweep_signed_test(unsigned m, const SweepChunk<D>& c, pt::f3 rd, pt::f3 ol, pt::f3 oh, float t0, float c_lo) {
+    PT_SWEEP_UNROLL
+    for (int j = 0; j < D; j++)
+        m = sweep_push(m, sweep_hit_signed(c.q[j][0], c.q[j][1], c.q[j][2], c.q[j][3], c.q[j][4], c.q[j][5], rd, ol, oh, t0, c_lo));
+    return m;
+}
+template <int D, class P>
+PT_HD unsigned sweep_mask_signed_piped(pt::f3 rd, pt::f3 ol, pt::f3 oh, float t0, float c_lo, P px, P py, P pz, int n) {
+    static_assert(D >= 1 && D <= 8, "boxes in flight");
+    unsigned m = 0u;
+    int k = n - 1;
+    for (int j = n % D; j > 0; j--, k--) {
+        SweepChunk<1> c;
+        sweep_signed_load(c, px, py, pz, k);
+        m = sweep_signed_test(m, c, rd, ol, oh, t0, c_lo);
+    }
+    if (k < 0) return m;
+    SweepChunk<D> ca, cb;       // k + 1 is a multiple of D: whole chunks from here, the one at k in ca
+    sweep_signed_load(ca, px, py, pz, k);
+    for (; k >= 3 * D - 1; k -= 2 * D) {    // two more chunks below
+        sweep_signed_load(cb, px, py, pz, k - D);
+        sweep_issue_fence();
+        m = sweep_signed_test(m, ca, rd, ol, oh, t0, c_lo);
+        sweep_signed_load(ca, px, py, pz, k - 2 * D);
+        sweep_issue_fence();
+        m = sweep_signed_test(m, cb, rd, ol, oh, t0, c_lo);
+    }
+    if (k >= 2 * D - 1) {                   // one more
+        sweep_signed_load(cb, px, py, pz, k - D);
+        m = sweep_signed_test(m, ca, rd, ol, oh, t0, c_lo);
+        return sweep_signed_test(m, cb, rd, ol, oh, t0, c_lo);
+    }
+    return sweep_signed_test(m, ca, rd, ol, oh, t0, c_lo);
 }
 // The sweep's first test where the camera stands outside the scene (KParams::sweep_root): the root box, by the same
 // test.  Every leaf box lies inside it (a nested tree), the reference reaches a leaf only past the root's exact test

@@ -300,9 +300,11 @@ LaunchPlan plan_launch(const SceneFacts& f, const Tuning& t, const Image& im, co
         // +4.3%, 16-frame +5.0%, 64-frame +5.6%); overlapped launches were not measured with the pool.  The pool runs only at that occupancy, the one
         // its constants were measured at: one wave per SIMD fewer already loses to k_render_sm (128 x 256 at 3 waves:
         // -5% on C2), so a scene whose trimmed copy costs a workgroup per CU (more than about 5.6 KB) keeps k_render_sm.
+        // The leaf boxes are staged as the signed table the sweep reads by ray sign, 3 quads per leaf (pt_cull.h; the
+        // exact re-test reads its positive variants): Cornell 3,728 B; 24 leaves of 48 slots and 13 materials 4,880 B.
         p.pool_paths = kPoolPaths, p.pool_nt = kPoolThreads;
         const int wpb = kPoolThreads / 64;
-        const size_t scene = (size_t)(4 * f.n_slots + 3 * f.n_mats + 2 * f.n_spheres + 2 * f.n_leaves) * 16;
+        const size_t scene = (size_t)(4 * f.n_slots + 3 * f.n_mats + 2 * f.n_spheres + 3 * f.n_leaves) * 16;
         p.pool_lds_bytes = ptpool::block_bytes(kPoolPaths, wpb, scene);
         const int full_cu = 4 * kPoolWaves / wpb;
         const int per_cu = (int)std::min<size_t>(kLdsCu / (p.pool_lds_bytes + 1024), (size_t)full_cu);

@@ -240,6 +240,25 @@ __device__ __forceinline__ unsigned sweep_candidates(const KParams& p, const Sce
     return cand;
 }
 
+// The same candidates from the workgroup's signed table in LDS (ptc::sweep_mask_signed_piped; `pairs`: the table as
+// 8-byte pairs): the ray's signs choose three read addresses once per segment instead of six selects, and a box costs
+// 6 fmas.  The root box's test, wave-uniform and rare, keeps the split reciprocal.
+template <int DEPTH>
+__device__ __forceinline__ unsigned sweep_candidates_signed(const KParams& p, const SceneView& S, const float2* pairs,
+                                                            bool on, f3 o, f3 rd, float t) {
+    unsigned cand = 0u;
+    if (on) {
+        f3 ol, oh;
+        ptc::cull_addends(o, rd, S.cm, S.ws, ol, oh);
+        bool in = true;
+        if (p.sweep_root) in = ptc::sweep_root_hit(p.root_box, ptc::sweep_ray(rd, ol, oh), t, S.clo);
+        if (in) cand = ptc::sweep_mask_signed_piped<DEPTH>(rd, ol, oh, t, S.clo, pairs + ptc::sweep_signed_pair(rd.x, 0),
+                                                           pairs + ptc::sweep_signed_pair(rd.y, 1),
+                                                           pairs + ptc::sweep_signed_pair(rd.z, 2), p.n_sweep);
+    }
+    return cand;
+}
+
 // A leaf's 2-way choice (:406-429) between its triangles' hits h1, h2 (-1: a miss) against the segment's t.
 struct LeafChoice { bool c1, c2; };
 __device__ __forceinline__ LeafChoice leaf_choice(float h1, float h2, float t) {

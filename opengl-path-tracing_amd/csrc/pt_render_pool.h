@@ -33,6 +33,22 @@
 #ifndef PT_POOL_SWEEP_LDS
 #define PT_POOL_SWEEP_LDS 1
 #endif
+// Round 17: the sweep reads each box's bounds near-first by the ray's signs from a signed table the
+// workgroup builds in LDS (pt_cull.h, "the signed sweep table"): 6 fmas per box instead of 12 and three 8-byte reads
+// instead of two broadcast 16-byte ones.  The signed table takes the place of the {lo, hi} copy, 3 quads per leaf
+// instead of 2: the exact leaf re-test assembles its operands from the table's positive variants, the same floats
+// (both tables side by side would cost a 24-leaf scene of 13 materials, one of the pinned fuzz soups, a workgroup per CU).
+//   PT_POOL_SWEEP_SIGNED 1: ptc::sweep_mask_signed_piped at PT_POOL_SWEEP_DEPTH boxes per chunk (needs the LDS form and
+//                        a depth above 0); 0: the round-16 loop on the {lo, hi} copy, for the same-process A/B
+//                        (profiles/ab/r17_signed_sweep/); the planner's LDS account is the signed table's either way
+// Same-process A/B against the parent (a copy of it: -0.05..+0.5%): +4.3% and +4.9% on C2's 1024-frame launch, +4.3% on the
+// 1080p/8 share; depth 3 / 4 gain 3.6 / 2.7%, so depth 2 stays.  Per trip of four boxes the loop is 24 v_fma_f32, six
+// ds_read2_b64 with immediate offsets, no v_cndmask and 4 address adds; 93 VGPRs.  Wave-VALU per segment 22.93 -> 21.69;
+// the LDS array is busier than with the broadcast reads (60.6% -> 70.7% of the launch), not idler.
+#ifndef PT_POOL_SWEEP_SIGNED
+#define PT_POOL_SWEEP_SIGNED 1
+#endif
+#define PT_POOL_SIGNED_ON (PT_POOL_SWEEP_SIGNED && PT_POOL_SWEEP_LDS && PT_POOL_SWEEP_DEPTH > 0)
 namespace {
 
 // The reference walk and leaf tests for a ray outside the exact-reciprocal guard (a few thousand of C2's segments),
@@ -84,12 +100,24 @@ __global__ __launch_bounds__(NT, MINW) void k_render_pool(KParams p) {
     resolve_frames(p);
     extern __shared__ float4 lds[];
     // staged: what swept rays read -- the triangle slots in chain order (planes), materials, the sphere, and the
-    // leaf boxes for the exact re-test (the sweep table's own records: axis-paired, chain order)
-    const int T = p.n_slots, nt = 4 * T, nm = 3 * p.n_mats, ns = 2, nb = 2 * p.n_sweep;
+    // leaf boxes in chain order: the signed table (ptc::kSignedQuads per leaf: the sweep's reads and, by its positive
+    // variants, the exact re-test's), or without it the sweep table's own axis-paired records
+    const int T = p.n_slots, nt = 4 * T, nm = 3 * p.n_mats, ns = 2, nb = ptc::kSignedQuads * p.n_sweep;
     stage_tris_chain_order(lds, p, T, NT);
     for (int i = threadIdx.x; i < nm; i += NT) lds[nt + i] = p.sc.mats[i];
     for (int i = threadIdx.x; i < ns; i += NT) lds[nt + nm + i] = p.sc.spheres[i];
-    for (int i = threadIdx.x; i < nb; i += NT) lds[nt + nm + ns + i] = p.sweep_tab[i];
+#if PT_POOL_SIGNED_ON
+    for (int leaf = threadIdx.x; leaf < p.n_sweep; leaf += NT) {    // (a thread per leaf: at most 32 of them, once)
+        const float4 a = p.sweep_tab[2 * leaf], b = p.sweep_tab[2 * leaf + 1];
+        for (int axis = 0; axis < ptc::kSignedQuads; axis++) {
+            float q[4];
+            ptc::sweep_signed_quad(a, b, axis, q);
+            lds[nt + nm + ns + ptc::kSignedQuads * leaf + axis] = make_float4(q[0], q[1], q[2], q[3]);
+        }
+    }
+#else
+    for (int i = threadIdx.x; i < 2 * p.n_sweep; i += NT) lds[nt + nm + ns + i] = p.sweep_tab[i];
+#endif
     const int scene_q = nt + nm + ns + nb;
     const int lane = (int)(threadIdx.x & 63u);
     float4* const pool = lds + scene_q + (int)(threadIdx.x >> 6) * (wave_bytes(P) / 16);
@@ -109,6 +137,8 @@ __global__ __launch_bounds__(NT, MINW) void k_render_pool(KParams p) {
     S.mats = lds + nt;
     S.spheres = lds + nt + nm;
     const float4* const boxes = lds + nt + nm + ns;
+    const float2* const signed_pairs = (const float2*)boxes;
+    (void)signed_pairs;
     S.np = 0;
     S.tp = T;
     S.cm[0] = p.cons_m[0], S.cm[1] = p.cons_m[1], S.cm[2] = p.cons_m[2];
@@ -206,7 +236,9 @@ __global__ __launch_bounds__(NT, MINW) void k_render_pool(KParams p) {
                     }
                 }
                 const bool walk = !ray_has_nan(o, d);     // (a sweeping launch has nodes and triangles)
-#if PT_POOL_SWEEP_DEPTH > 0 && PT_POOL_SWEEP_LDS
+#if PT_POOL_SIGNED_ON
+                const unsigned cand = sweep_candidates_signed<PT_POOL_SWEEP_DEPTH>(p, S, signed_pairs, walk & fast_seg, o, rd, t);
+#elif PT_POOL_SWEEP_DEPTH > 0 && PT_POOL_SWEEP_LDS
                 const unsigned cand = sweep_candidates<PT_POOL_SWEEP_DEPTH>(p, S, boxes, walk & fast_seg, o, rd, t);
 #else
                 const unsigned cand = sweep_candidates<PT_POOL_SWEEP_DEPTH>(p, S, sweep_tab, walk & fast_seg, o, rd, t);
@@ -260,7 +292,14 @@ __global__ __launch_bounds__(NT, MINW) void k_render_pool(KParams p) {
             if (__any(chk)) {
                 if (chk) {
                     const f3 rd = mk(pt::rcp_fast(d.x), pt::rcp_fast(d.y), pt::rcp_fast(d.z));
+#if PT_POOL_SIGNED_ON
+                    // (lo, hi) per axis: the first pair of each of the leaf's three signed quads
+                    const float2 bx = signed_pairs[ptc::kSignedPairs * lp], by = signed_pairs[ptc::kSignedPairs * lp + 2];
+                    const float2 bz = signed_pairs[ptc::kSignedPairs * lp + 4];
+                    if (!slab_fast(make_float4(bx.x, bx.y, by.x, by.y), make_float4(bz.x, bz.y, 0, 0), o, d, rd, t)) c1h = c2h = false;
+#else
                     if (!slab_fast(boxes[2 * lp], boxes[2 * lp + 1], o, d, rd, t)) c1h = c2h = false;
+#endif
                 }
             }
             if (at) {
