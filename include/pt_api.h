@@ -378,6 +378,58 @@ int pt_read_guides(pt_ctx* ctx, float* host_dst, size_t bytes);
 int pt_denoise_host(const float* image, const float* variance, const float* guides, const unsigned char* in_footprint,
                     int W, int H, const pt_denoise_params* params, float* out);
 
+/* Ray queries: what a caller's ray hits in the uploaded scene -- picking, focus distance, visibility
+ * and occlusion probes, collision -- on the resident BVH and with the render's bit-exact walk.
+ *
+ * The result of a ray is the reference's calculateRayCollision (computeShader.c:367-432) with t starting at t_max
+ * instead of 1./0.: the spheres in index order, accepting 1e-4 < t_s < t, then the link walk from node 0 with
+ * bvh_intersect at the current t and the 2-way choice at every hit leaf.  d is used as given, not normalised.  The
+ * context's PT_FLAG_NO_SPHERES, PT_FLAG_NO_TRIANGLES and PT_FLAG_MOLLER_TRUMBORE apply as in a render.  t_max = +inf
+ * is exactly the reference; a NaN or too-small t_max, NaN or zero ray components and an origin inside a sphere get no
+ * special case and fall out of the IEEE arithmetic as they do there.  With PT_QUERY_ANY_HIT (occlusion) the ray stops
+ * at the first acceptance in that same order and reports it: deterministic too.
+ *
+ * A query is invisible to rendering: it takes no timing events, touches no launch counter, tile order, moments,
+ * presented state or captured graph, and writes nothing a render reads. */
+typedef struct {
+    float o[3];
+    float t_max;
+    float d[3];
+    float pad;               /* 0 */
+} pt_ray;                    /* 32 B */
+#define PT_HIT_NONE 0
+#define PT_HIT_SPHERE 1
+#define PT_HIT_TRIANGLE 2
+typedef struct {
+    float t;                 /* +inf for a miss */
+    int kind;                /* PT_HIT_* */
+    int prim;                /* the sphere index, or the triangle index of the uploaded array (the leaf's data[0] /
+                                data[1] that won); -1 for a miss */
+    int mat;                 /* the material index; -1 for a miss */
+    float n[4];              /* the reference's normal, flipped against d; n[3] = 0 */
+    float p[4];              /* o + t*d, the multiply and the add rounded separately (hitPoint); p[3] = 0 */
+} pt_hit;                    /* 48 B; a miss has n = p = 0 */
+#define PT_QUERY_ANY_HIT 1
+/* n rays from host arrays, synchronous.  PT_E_STATE before pt_upload_scene, PT_E_ARG for a null array with n > 0, a
+ * negative n or unknown query flags; n = 0 is PT_OK without a launch.  A row-split context (world > 1) answers like
+ * any other: every context holds the whole scene. */
+int pt_intersect(pt_ctx* ctx, const pt_ray* rays, long long n, pt_hit* hits, int query_flags);
+/* The same on device arrays (16-byte aligned), enqueued on the context's stream (pt_stream) behind the renders and
+ * accumulate passes already enqueued, and not synchronised. */
+int pt_intersect_device(pt_ctx* ctx, const void* d_rays, long long n, void* d_hits, int query_flags);
+/* The camera rays of n pixels xy = {x0, y0, x1, y1, ...} (image row 0 = bottom) as a render with PT_FLAG_NO_AA
+ * forms them: zero jitter, the camera basis as pt_set_camera derives it from cam, t_max = +inf.  Pure host code. */
+int pt_pixel_rays(int width, int height, const float cam[12], const int* xy, long long n, pt_ray* rays_out);
+/* pt_pixel_rays with the context's camera and size, then pt_intersect: what is under these pixels (a context
+ * starts with the reference's default camera). */
+int pt_pick(pt_ctx* ctx, const int* xy, long long n, pt_hit* hits);
+/* The query on the host, of a scene in pt_upload_scene's arrays: packs it as pt_upload_scene does and runs the device
+ * kernel's own per-ray code on the packed buffers.  No device is touched.  ctx_flags: the PT_FLAG_* a context would
+ * hold.  Returns the packer's error for a rejected scene. */
+int pt_intersect_host(const float* tris, int n_tris, const float* bvh, int n_nodes, const float* mats, int n_mats,
+                      const float* spheres, int n_spheres, int ctx_flags, const pt_ray* rays, long long n,
+                      pt_hit* hits, int query_flags);
+
 #ifdef __cplusplus
 }
 #endif

@@ -63,7 +63,14 @@ static void usage() {
                  "  --denoise       after rendering, filter the image (pt_api.h: pt_denoise; one context) with\n"
                  "                  --denoise-iters N iterations (default 5) over guides of --guide-frames G\n"
                  "                  frames (default 4); --denoise-pfm F / --denoise-ppm F write the result as\n"
-                 "                  the RGBA32F PFM / the ACES PPM; --json gains a \"denoise\" object\n");
+                 "                  the RGBA32F PFM / the ACES PPM; --json gains a \"denoise\" object\n"
+                 "  --pick X,Y      what is under pixel (X, Y), row 0 = bottom (pt_api.h: pt_pick; repeatable): one\n"
+                 "                  JSON line per pixel with kind (0 miss, 1 sphere, 2 triangle), prim, mat, t, n,\n"
+                 "                  p and the material's albedo (t and albedo null for a miss)\n"
+                 "  --rays F --hits G [--any-hit]  cast the raw 32-byte rays of F (pt_api.h: pt_ray, pt_intersect)\n"
+                 "                  and write the raw 48-byte hit records to G\n"
+                 "                  queries run on context 0 after the render; without --spp, --noise-target and\n"
+                 "                  --events they run alone: nothing is rendered and no image is written\n");
 }
 
 // Checkpoint of a progressive render (SURVEY.md §5 checkpoint / resume): the running mean
@@ -198,12 +205,15 @@ int main(int argc, char** argv) {
     pt_denoise_info dinfo = {0, 0, 0, 0};
     std::string denoise_pfm, denoise_ppm;
     double denoise_ms = 0.0;
+    std::vector<int> picks;               // x, y pairs
+    std::string rays_path, hits_path;
+    bool any_hit = false, spp_given = false;
     for (int i = 3; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&](void) -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
         if (a == "--width") W = std::atoi(next());
         else if (a == "--height") H = std::atoi(next());
-        else if (a == "--spp") spp = std::atoi(next());
+        else if (a == "--spp") { spp = std::atoi(next()); spp_given = true; }
         else if (a == "--chunk") chunk = std::atoi(next());
         else if (a == "--bounces") bounces = std::atoi(next());
         else if (a == "--mode") mode = std::atoi(next());
@@ -228,6 +238,15 @@ int main(int argc, char** argv) {
         else if (a == "--guide-frames") dparams.guide_frames = std::atoi(next());
         else if (a == "--denoise-pfm") denoise_pfm = next();
         else if (a == "--denoise-ppm") denoise_ppm = next();
+        else if (a == "--pick") {
+            int x = 0, y = 0;
+            if (std::sscanf(next(), "%d,%d", &x, &y) != 2) { usage(); return 2; }
+            picks.push_back(x);
+            picks.push_back(y);
+        }
+        else if (a == "--rays") rays_path = next();
+        else if (a == "--hits") hits_path = next();
+        else if (a == "--any-hit") any_hit = true;
         else { usage(); return 2; }
     }
     if (ranks == 0) ranks = gpus;
@@ -244,6 +263,12 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--denoise-pfm / --denoise-ppm need --denoise\n");
         return 2;
     }
+    if (rays_path.empty() != hits_path.empty() || (any_hit && rays_path.empty())) {
+        std::fprintf(stderr, "--rays and --hits go together, --any-hit with them\n");
+        return 2;
+    }
+    const bool queries = !picks.empty() || !rays_path.empty();
+    const bool query_only = queries && !spp_given && !until && !events && !denoise && resume.empty() && checkpoint.empty();
     if (adaptive && !until) {
         std::fprintf(stderr, "--adaptive needs --noise-target\n");
         return 2;
@@ -328,6 +353,47 @@ int main(int argc, char** argv) {
                 std::memcpy(&part[4 * (size_t)k * W], &prior[4 * (size_t)(r0 + k * rs) * W], 16 * (size_t)W);
             CHECK(pt_write_rgba32f(ctx[g], part.data(), part.size() * 4), ctx[g]);
         }
+    }
+    // the ray queries (--pick, --rays / --hits), on context 0: every context holds the whole scene
+    auto run_queries = [&]() -> int {
+        if (!picks.empty()) {
+            std::vector<pt_hit> h(picks.size() / 2);
+            CHECK(pt_pick(ctx[0], picks.data(), (long long)h.size(), h.data()), ctx[0]);
+            for (size_t i = 0; i < h.size(); i++) {
+                std::printf("{\"pick\": [%d, %d], \"kind\": %d, \"prim\": %d, \"mat\": %d, ", picks[2 * i], picks[2 * i + 1],
+                            h[i].kind, h[i].prim, h[i].mat);
+                if (h[i].kind == PT_HIT_NONE) std::printf("\"t\": null, ");
+                else std::printf("\"t\": %.9g, ", h[i].t);
+                std::printf("\"n\": [%.9g, %.9g, %.9g], \"p\": [%.9g, %.9g, %.9g], ", h[i].n[0], h[i].n[1], h[i].n[2],
+                            h[i].p[0], h[i].p[1], h[i].p[2]);
+                if (h[i].kind == PT_HIT_NONE) std::printf("\"albedo\": null}\n");
+                else std::printf("\"albedo\": [%.9g, %.9g, %.9g]}\n", mats[16 * (size_t)h[i].mat], mats[16 * (size_t)h[i].mat + 1],
+                                 mats[16 * (size_t)h[i].mat + 2]);
+            }
+        }
+        if (!rays_path.empty()) {
+            FILE* f = std::fopen(rays_path.c_str(), "rb");
+            if (!f) { std::fprintf(stderr, "cannot read %s\n", rays_path.c_str()); return 1; }
+            std::vector<pt_ray> rays;
+            pt_ray r;
+            while (std::fread(&r, sizeof(r), 1, f) == 1) rays.push_back(r);
+            std::fclose(f);
+            std::vector<pt_hit> h(rays.size());
+            CHECK(pt_intersect(ctx[0], rays.data(), (long long)rays.size(), h.data(), any_hit ? PT_QUERY_ANY_HIT : 0), ctx[0]);
+            f = std::fopen(hits_path.c_str(), "wb");
+            if (!f || std::fwrite(h.data(), sizeof(pt_hit), h.size(), f) != h.size()) {
+                std::fprintf(stderr, "cannot write %s\n", hits_path.c_str());
+                return 1;
+            }
+            std::fclose(f);
+        }
+        return 0;
+    };
+    if (query_only) {
+        const int qrc = run_queries();
+        pt_group_destroy(group);
+        for (int g = 0; g < nctx; g++) pt_destroy(ctx[g]);
+        return qrc;
     }
     auto t1 = std::chrono::steady_clock::now();
     int frames_run = 0, resets = 0;
@@ -429,6 +495,7 @@ int main(int argc, char** argv) {
         CHECK(pt_read_denoised_rgba32f(ctx[0], dimg.data(), dimg.size() * 4), ctx[0]);
         CHECK(pt_read_denoised_rgba8_aces(ctx[0], drgba.data(), drgba.size()), ctx[0]);
     }
+    if (queries && run_queries()) return 1;
     pt_group_destroy(group);
     for (int g = 0; g < nctx; g++) pt_destroy(ctx[g]);
     std::printf("rendered %dx%d, %d spp, %d bounces on %d GPU(s), %d context(s): %.3f s, %.3f ms/frame\n", W, H, spp,

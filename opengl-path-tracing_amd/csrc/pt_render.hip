@@ -27,6 +27,7 @@
 #include "pt_math.h"
 #include "pt_noise.h"
 #include "pt_pool.h"
+#include "pt_query_launch.h"
 #include "pt_render_kernels.h"
 #include "pt_scene_pack.h"
 #include "pt_wide.h"
@@ -1019,6 +1020,24 @@ int pt__scene_set_ready(pt_ctx* c, int ready) {
     c->scene_ok = ready != 0 && c->d_scene[ptp::kMats] != nullptr;
     return PT_OK;
 }
+
+// The ray query's view of a context (pt_query_kernels.hip; internal, not part of the public ABI): the scene buffers
+// and facts a cast reads, the context's flags, camera basis, size and stream.  Changes nothing in the context -- a
+// query stays invisible to rendering.
+int pt__query_view(const pt_ctx* c, ptq::CtxView* out) {
+    if (!c || !out) return PT_E_ARG;
+    const float4* const* d = c->d_scene;
+    out->nodes = d[ptp::kNodes], out->tris = d[ptp::kTris], out->spheres = d[ptp::kSpheres];
+    out->leaf_tris = d[ptp::kLeafTris];
+    out->n_nodes = c->sf.n_nodes, out->n_spheres = c->sf.n_spheres, out->scene_fast = c->sf.scene_fast;
+    out->flags = c->cfg.flags, out->kernel_variant = c->tun.variant;
+    out->device = c->cfg.device, out->width = c->cfg.width, out->height = c->cfg.height;
+    std::memcpy(out->cam, c->cam, sizeof(out->cam));
+    out->scene_ok = c->scene_ok && d[ptp::kLeafTris] != nullptr, out->cam_ok = c->cam_ok;
+    out->stream = c->stream;
+    return PT_OK;
+}
+int pt__query_fail(pt_ctx* c, int code, const char* msg) { return fail(c, code, msg ? msg : ""); }
 
 int pt_read_rgba32f(pt_ctx* c, float* dst, size_t bytes) {
     if (!c || !dst) return PT_E_ARG;

@@ -124,6 +124,7 @@ size_t buf_quads(const ptl::SceneFacts& f, int b) {
     case kWideNodes: return ni ? buf_quads(f, kNodes) : 0;
     case kWideTris: return 8 * ni;
     case kSweep: return f.sweep_ok ? 2 * (size_t)f.n_leaves : 0;
+    case kLeafTris: return (size_t)std::max(f.n_slots / 2, 1);
     default: return 0;
     }
 }
@@ -151,6 +152,7 @@ int pack_scene(const float* tris, int n_tris, const float* bvh, int n_nodes, con
     std::vector<unsigned char> cop_of(n_nodes, 0);   // coplanar leaf pair, by reference node index
     Quad* const dn = quads(kNodes, 2 * (size_t)std::max(n_nodes, 1));
     Quad* const dt = quads(kTris, 8 * (size_t)std::max(n_leaves, 1));
+    Quad* const dlt = quads(kLeafTris, (size_t)std::max(n_leaves, 1));
     for (int i = 0; i < n_nodes; i++) {
         const float* nd = bvh + 12 * (size_t)i;
         int a, b;
@@ -159,6 +161,7 @@ int pack_scene(const float* tris, int n_tris, const float* bvh, int n_nodes, con
             int t0 = (int)nd[8], t1 = (int)nd[9];
             put_tri(&dt[8 * (size_t)s], tris + 16 * (size_t)t0);
             put_tri(&dt[8 * (size_t)s + 4], tris + 16 * (size_t)t1);
+            dlt[s] = {as_float(t0), as_float(t1), 0.0f, 0.0f};
             const bool cop = same_plane(dt[8 * (size_t)s], dt[8 * (size_t)s + 4]);
             a = ~((s << 2) | (cop ? 2 : 0) | (t0 == t1 ? 1 : 0));
             cop_of[i] = cop ? 1 : 0;

@@ -33,6 +33,9 @@ enum SceneBuf {
     // them -- 2 quads, {lo.x, hi.x, lo.y, hi.y}, {lo.z, hi.z, its pair index, the chain position of pair k (the
     // inverse map)}; only for a scene with sweep_ok.  A sweeping kernel stages the triangle slots in chain order.
     kSweep = kBufs,
+    // the ray query's leaf table (pt_query.h): per leaf slot pair k one quad {tri0, tri1, 0, 0} as integer bits, the
+    // reference triangle indices (b.data[0], b.data[1]) a hit record reports
+    kLeafTris,
     kBufsAll       // every device buffer of a scene
 };
 

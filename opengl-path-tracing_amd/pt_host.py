@@ -186,6 +186,11 @@ def lib():
             "pt_read_denoised_rgba8_aces": (ip, [vp, vp, C.c_size_t]),
             "pt_read_guides": (ip, [vp, vp, C.c_size_t]),
             "pt_denoise_host": (ip, [_F, vp, _F, vp, ip, ip, C.POINTER(DenoiseParams), _F]),
+            "pt_intersect": (ip, [vp, vp, C.c_longlong, vp, ip]),
+            "pt_intersect_device": (ip, [vp, vp, C.c_longlong, vp, ip]),
+            "pt_pixel_rays": (ip, [ip, ip, _F, vp, C.c_longlong, vp]),
+            "pt_pick": (ip, [vp, vp, C.c_longlong, vp]),
+            "pt_intersect_host": (ip, [_F, ip, _F, ip, _F, ip, _F, ip, ip, vp, C.c_longlong, vp, ip]),
             "pt_group_create": (ip, [C.POINTER(vp), ip, C.POINTER(vp)]),
             "pt_group_destroy": (None, [vp]),
             "pt_group_last_error": (C.c_char_p, [vp]),
@@ -630,6 +635,28 @@ class PathTracer:
         self._check(lib().pt_read_guides(self.h, out.ctypes.data, out.nbytes))
         return out
 
+    def intersect(self, rays, any_hit=False):
+        """pt_intersect: what each ray hits (RAY_DTYPE or (n, 8) float32 rays -> HIT_DTYPE), synchronous."""
+        rays = _rays_in(rays)
+        hits = np.zeros(len(rays), HIT_DTYPE)
+        self._check(lib().pt_intersect(self.h, rays.ctypes.data, len(rays), hits.ctypes.data,
+                                       PT_QUERY_ANY_HIT if any_hit else 0))
+        return hits
+
+    def intersect_device(self, rays_ptr, n, hits_ptr, any_hit=False):
+        """pt_intersect_device: n rays at device pointer rays_ptr (32 B each) -> hits at hits_ptr (48 B each), e.g.
+        the data_ptr() of torch tensors of shapes (n, 8) / (n, 12) float32; enqueued on the context's stream
+        (stream()), not synchronised."""
+        self._check(lib().pt_intersect_device(self.h, C.c_void_p(int(rays_ptr)), int(n), C.c_void_p(int(hits_ptr)),
+                                              PT_QUERY_ANY_HIT if any_hit else 0))
+
+    def pick(self, xy):
+        """pt_pick: the closest hit under each of the (n, 2) pixels xy (row 0 = bottom) -> HIT_DTYPE."""
+        xy = _xy_in(xy)
+        hits = np.zeros(len(xy), HIT_DTYPE)
+        self._check(lib().pt_pick(self.h, xy.ctypes.data, len(xy), hits.ctypes.data))
+        return hits
+
     def diag(self):
         """Lane utilisation per kernel phase from the last counting render."""
         v = np.zeros(16, np.uint64)
@@ -800,6 +827,70 @@ class Group:
         if getattr(self, "h", None) is not None and self.h.value:
             lib().pt_group_destroy(self.h)
         self.h = C.c_void_p()
+
+
+# ----------------------------------------------------------------------------- ray queries
+PT_HIT_NONE, PT_HIT_SPHERE, PT_HIT_TRIANGLE = 0, 1, 2
+PT_QUERY_ANY_HIT = 1
+RAY_DTYPE = np.dtype([("o", np.float32, 3), ("t_max", np.float32), ("d", np.float32, 3), ("pad", np.float32)])
+HIT_DTYPE = np.dtype([("t", np.float32), ("kind", np.int32), ("prim", np.int32), ("mat", np.int32),
+                      ("n", np.float32, 4), ("p", np.float32, 4)])
+
+
+def make_rays(o, d, t_max=np.inf):
+    """n rays as a RAY_DTYPE array from (n, 3) origins and directions and a t_max (scalar or (n,))."""
+    o = np.asarray(o, np.float32).reshape(-1, 3)
+    r = np.zeros(len(o), RAY_DTYPE)
+    r["o"], r["d"], r["t_max"] = o, np.asarray(d, np.float32).reshape(-1, 3), t_max
+    return r
+
+
+def _rays_in(rays):
+    """Rays as a contiguous RAY_DTYPE array: structured already, or (n, 8) float32."""
+    a = np.asarray(rays)
+    if a.dtype == RAY_DTYPE:
+        return np.ascontiguousarray(a).reshape(-1)
+    a = np.ascontiguousarray(a, np.float32)
+    if a.ndim != 2 or a.shape[1] != 8:
+        raise ValueError("rays must be a RAY_DTYPE array or (n, 8) float32")
+    return a.view(RAY_DTYPE).reshape(-1)
+
+
+def _xy_in(xy):
+    a = np.ascontiguousarray(xy, np.int32)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError("xy must be (n, 2) pixel coordinates")
+    return a
+
+
+def hits_words(hits):
+    """The (n, 12) uint32 words of a HIT_DTYPE array (for bit-for-bit comparisons)."""
+    return np.ascontiguousarray(hits).view(np.uint32).reshape(-1, 12)
+
+
+def pixel_rays(width, height, cam, xy):
+    """pt_pixel_rays: the PT_FLAG_NO_AA camera rays of the (n, 2) pixels xy (row 0 = bottom), on the host."""
+    xy = _xy_in(xy)
+    rays = np.zeros(len(xy), RAY_DTYPE)
+    rc = lib().pt_pixel_rays(int(width), int(height), np.ascontiguousarray(cam, np.float32).reshape(12),
+                             xy.ctypes.data, len(xy), rays.ctypes.data)
+    if rc:
+        raise PTError(rc, "pt_pixel_rays: bad size or arrays")
+    return rays
+
+
+def intersect_host(sb, rays, any_hit=False, flags=0):
+    """pt_intersect_host: the ray query on the host (no device) -- the per-ray code is the device kernel's own,
+    run on the buffers ptp::pack_scene makes of the scene `sb`.  flags: the PT_FLAG_* of a context."""
+    rays = _rays_in(rays)
+    hits = np.zeros(len(rays), HIT_DTYPE)
+    t, n, m, s = _f32(sb["tris"], 16), _f32(sb["nodes"], 12), _f32(sb["mats"], 16), _f32(sb["spheres"], 8)
+    z = lambda a, c: a.reshape(-1) if a.size else np.zeros(c, np.float32)
+    rc = lib().pt_intersect_host(z(t, 16), len(t), z(n, 12), len(n), z(m, 16), len(m), z(s, 8), len(s), int(flags),
+                                 rays.ctypes.data, len(rays), hits.ctypes.data, PT_QUERY_ANY_HIT if any_hit else 0)
+    if rc:
+        raise PTError(rc, "pt_intersect_host: rejected scene or bad arguments")
+    return hits
 
 
 def noise_host(moments, frames, target, in_footprint=None):
