@@ -57,123 +57,9 @@ using ptl::kPullBatch;
 
 // ===================================================================== host side
 // Launch policy (LDS staging, workgroup, group, queue batch, the kernel key) lives in
-// pt_launch_plan.{h,cpp}; this file fills KParams from its plan and does the stateful work.
-using ptl::kAutoSlots;
-using ptl::kMaxSlots;
-using ptl::kShortLaunch;
-// Scratch ring of overlapped launches: each launch takes the next entry (colour scratch, queue
-// head, render / accumulate events) of a ring kRingMult times as long as the render streams, so
-// a render waits for the accumulate pass of the launch kRingMult * slots back, not of the one
-// that last used its stream (which the stream order already puts before it).
-constexpr int kRingMult = 2, kRingMax = kRingMult * kMaxSlots;
-constexpr size_t kQueueSet = kQueueStride;   // unsigned per queue head
-
-constexpr int kPresentBufs = 4;   // pt_present_begin buffers
-
-struct pt_ctx {
-    pt_config cfg{};
-    int rows_local = 0;
-    hipStream_t stream = nullptr;
-    std::vector<hipEvent_t> ev_free;                               // recycled events
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pending;     // launches not yet synced
-    double total_ms = 0.0;
-    int n_launches = 0;
-    float4* accum = nullptr;
-    uchar4* rgba8 = nullptr;
-    float4* d_scene[ptp::kBufsAll] = {};   // the device scene (ptp::SceneBuf); null: the scene has no such buffer
-    ptl::SceneFacts sf;             // what ptp::pack_scene learned (the launch planner's input)
-    ptl::Tuning tun;                // pt_set_tuning values and the kernel variant
-    unsigned long long* d_counters = nullptr;
-    unsigned int* d_work = nullptr;
-    int* d_frame = nullptr;                      // progressive graph frame counter
-    // adaptive queue order ("longest first"): per-tile segment counts measured by the
-    // previous renders order the next render's 8x8 tiles so cheap tiles form the tail
-    unsigned* d_tile_cost = nullptr;
-    unsigned* d_tile_perm = nullptr;
-    int n_tiles = 0, tiles_x = 1;
-    int tile_shift = 0, tile_key = 0;   // tile shape (KParams::tile_shift) and tuning key 20 (0 = automatic)
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t graph_exec = nullptr;
-    int graph_frames = 0;
-    unsigned persist_blocks = 2048;
-    int order_skip = 0;             // short launches since the last tile-order sort
-    bool order_sorted = false;      // a sort ran since the scene upload
-    // k_tile_order launches since the scene upload (pt_debug_tile_order): enqueued directly, and
-    // per replay of the captured graph
-    unsigned long long n_sorts = 0, graph_sorts = 0;
-    int n_cu = 0;
-    float* d_rgb = nullptr;        // per-(frame, pixel) colours of the frame-split mode
-    size_t rgb_bytes = 0;
-    // overlapped short launches (enqueue_render): the render kernels of consecutive short
-    // renders rotate over `tun.overlap_slots` streams with their own colour scratch and queue counter,
-    // so frame f+1 renders while frame f's launch drains; k_accum_frames stays on `stream`
-    // (created with the highest priority, so its small grid is dispatched as soon as render
-    // blocks retire) in frame order
-    hipStream_t rstream[kMaxSlots] = {};
-    float* slot_rgb[kRingMax] = {};
-    size_t slot_rgb_bytes[kRingMax] = {};
-    hipEvent_t ev_rdone[kRingMax] = {}, ev_adone[kRingMax] = {};
-    // main-stream fence an overlapped render waits for: recorded after every tile-order sort
-    // and graph replay (the writers of tile_perm, which the render reads)
-    hipEvent_t ev_fence = nullptr;
-    bool adone_rec[kRingMax] = {}, fence_rec = false;
-    int slot = 0;
-    int ring = 0;                   // next scratch-ring entry of an overlapped launch
-    // a captured graph bakes in the scratch pointer it was captured with: that buffer stays
-    // alive (owned here once ensure_rgb has moved on to a larger one) until drop_graph
-    float* graph_rgb = nullptr;
-    std::vector<float*> graph_owned;
-    bool scene_ok = false, cam_ok = false, counting = false;
-    float cam[12] = {0};
-    float last_ms = 0.0f;
-    unsigned long long last_counts[16] = {0};
-    unsigned long long n_line_launches[2] = {0, 0};   // render launches enqueued on a generic / a COMMON line (pt_debug_launches)
-    bool count_pending = false;
-    bool last_swept = false;        // the last render launch enqueued ran the leaf sweep (pt_debug_sweep)
-    bool last_pooled = false;       // ... ran k_render_pool (pt_debug_pool)
-    // asynchronous presentation (pt_present_begin / _end): per buffer a pinned host image and
-    // its copy event; the device view is rgba8 (one, as the copies and the passes that write
-    // it are ordered on the context stream)
-    unsigned char* present_host[kPresentBufs] = {};
-    hipEvent_t ev_copied[kPresentBufs] = {};
-    bool present_pending[kPresentBufs] = {};
-    // The accumulate pass writes the ACES view into rgba8 beside the running mean when the
-    // caller presented after the previous render (aces_fuse, from `presented`); stage_ok: rgba8
-    // holds the view of the current image (set by such a pass, cleared by anything that may
-    // change the image or rgba8 afterwards).
-    bool presented = false, aces_fuse = false, stage_ok = false;
-    // noise estimate (pt_set_moments): the luminance moments beside accum, the frames folded
-    // into them since the image last restarted (host count), and the summary's device block
-    // and pinned host copy (k_noise)
-    float2* moments = nullptr;
-    int mom_frames = 0;
-    pt_noise_stats* d_noise = nullptr;
-    pt_noise_stats* h_noise = nullptr;
-    // adaptive sampling (pt_render_adaptive): the moments hold per-tile frame counts since the last adaptive run
-    // (mom_frames is then the largest) until the image restarts; the per-tile frame map, the two lists of active
-    // tiles a batch reads and writes, and the call's summary block with its pinned host copy -- all sized by the tile
-    // grid and dropped with it (set_tiles)
-    bool mom_mixed = false;
-    unsigned* d_tile_frames = nullptr;
-    unsigned* d_active[2] = {nullptr, nullptr};
-    AdaptSum* d_adapt = nullptr;
-    AdaptSum* h_adapt = nullptr;
-    int adapt_done = 0;             // frames_done of the adaptive call the per-tile counts are from
-    // denoised view (pt_denoise): the two guide planes (N.rgb, Z) and (A.rgb, 0) with the guide_frames
-    // they hold, the filter's ping-pong state planes, its result and the result's ACES view.  The three rendered
-    // guide images pass through dn_state[0], dn_state[1] and dn_out on their way into the guide planes.
-    float4* dn_guide[2] = {nullptr, nullptr};
-    float4* dn_state[2] = {nullptr, nullptr};
-    float4* dn_out = nullptr;
-    uchar4* dn_rgba8 = nullptr;
-    bool guides_ok = false, dn_done = false;
-    int guides_frames = 0;
-    int dn_variant = 0;             // ptd::Variant (pt__denoise_debug; measurements only)
-    bool dn_timing = false;         // ... and events around the guide render, the prep and every iteration
-    hipEvent_t dn_ev[ptd::kMaxIterations + 3] = {};
-    int dn_ev_n = 0;
-    std::string err;
-};
+// pt_launch_plan.{h,cpp}; this file fills KParams from its plan and does the stateful work: the context's life,
+// scene, camera and settings, the tile grid, the render launch, the progressive graph.  The rest is its end's sections.
+#include "pt_ctx.h"            // struct pt_ctx, fail / HIPCHK, the helpers more than one section calls
 
 // Queue-order entry of linear tile t (row-major 8x8 tiles): (ty << 16) | tx, so the kernel
 // decodes a tile without an integer division.
@@ -181,21 +67,15 @@ static unsigned pack_tile(const pt_ctx* c, unsigned t) {
     return ((t / (unsigned)c->tiles_x) << 16) | (t % (unsigned)c->tiles_x);
 }
 
-
 static void drop_graph(pt_ctx* c);   // a captured graph bakes in scene/camera/config
-static int ensure_tiles(pt_ctx* c);  // the tile shape this context's next launch uses
 
-
-static int fail(pt_ctx* c, int code, const std::string& msg) {
-    if (c) c->err = msg;
-    return code;
+// The buffers sized by the tile grid (the adaptive ones are per tile too: allocated again on first use).
+static void free_tiles(pt_ctx* c) {
+    for (unsigned** b : {&c->d_tile_perm, &c->d_tile_cost, &c->d_tile_frames, &c->d_active[0], &c->d_active[1]}) {
+        (void)hipFree(*b);
+        *b = nullptr;
+    }
 }
-#define HIPCHK(ctx, call)                                                                   \
-    do {                                                                                    \
-        hipError_t e_ = (call);                                                             \
-        if (e_ != hipSuccess)                                                               \
-            return fail(ctx, PT_E_HIP, std::string(#call ": ") + hipGetErrorString(e_));     \
-    } while (0)
 
 // Tile shape of the work queue: 64 pixels as (8 << s) columns x (8 >> s) local rows (tuning
 // key 20; automatic: ensure_tiles).  Recomputes the tile count and resets the queue order.
@@ -204,13 +84,7 @@ static int set_tiles(pt_ctx* c, int s) {
     const int tw = 8 << s, th = 8 >> s;
     c->tiles_x = (c->cfg.width + tw - 1) / tw;
     c->n_tiles = c->tiles_x * ((c->rows_local + th - 1) / th);
-    (void)hipFree(c->d_tile_perm);
-    (void)hipFree(c->d_tile_cost);
-    c->d_tile_perm = c->d_tile_cost = nullptr;
-    (void)hipFree(c->d_tile_frames);      // the adaptive buffers are per tile: allocated again on first use
-    (void)hipFree(c->d_active[0]);
-    (void)hipFree(c->d_active[1]);
-    c->d_tile_frames = c->d_active[0] = c->d_active[1] = nullptr;
+    free_tiles(c);
     std::vector<unsigned> ident(std::max(c->n_tiles, 1));
     for (size_t i = 0; i < ident.size(); i++) ident[i] = pack_tile(c, (unsigned)i);
     HIPCHK(c, hipMalloc(&c->d_tile_perm, ident.size() * sizeof(unsigned)));
@@ -222,6 +96,19 @@ static int set_tiles(pt_ctx* c, int s) {
     return PT_OK;
 }
 
+// The work queue's tile shape (set_tiles): tuning key 20, else 8 x 8.  16 x 4 tiles for scenes
+// staged in LDS measured equal: with the builds in alternating order (ABBA, profiles/ab/
+// r06n_*) 16 x 4 and 8 x 8 are within 0.1% on C2 and C5; the +0.4..0.6% of the first A/Bs
+// (r06k_*, r06l_*, r06m_*) was tools/ab_inproc.py's first-position bias.  A shape change drains
+// the context's streams and drops a captured graph (which holds the tile arrays).
+static int ensure_tiles(pt_ctx* c) {
+    const int want = c->tile_key ? c->tile_key - 1 : 0;
+    if (want == c->tile_shift) return PT_OK;
+    HIPCHK(c, drain_streams(c));
+    drop_graph(c);
+    return set_tiles(c, want);
+}
+
 static void free_scene(pt_ctx* c) {
     for (float4*& d : c->d_scene) {
         (void)hipFree(d);
@@ -231,6 +118,10 @@ static void free_scene(pt_ctx* c) {
     c->sf.n_wide = 0;
     c->sf.sweep_ok = false;
     c->scene_ok = false;
+    c->order_sorted = false;      // the next sort pools the new scene's first short launches
+    c->order_skip = 0;
+    c->n_sorts = 0;
+    c->guides_ok = false;         // the guides are of the old scene
 }
 
 extern "C" {
@@ -274,15 +165,10 @@ int pt_create(const pt_config* cfg, pt_ctx** out) {
     HIPCHK(c, hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, cfg->device));
     c->persist_blocks = (unsigned)std::max(1, n_cu) * 8u;   // 8 x 256 threads = 32 waves per CU
     c->n_cu = std::max(1, n_cu);
-    {
-        size_t total_mem = 0;
-        HIPCHK(c, hipDeviceTotalMem(&total_mem, cfg->device));
-        c->tun.scratch_budget = std::min<size_t>(32ull << 30, total_mem / 4);
-    }
-    {
-        int rc = set_tiles(c, 0);   // 8 x 8 until a scene picks the automatic shape (ensure_tiles)
-        if (rc) return rc;
-    }
+    int rc = pt_set_tuning(c, 8, 0);   // the automatic scratch budget
+    if (rc) return rc;
+    rc = set_tiles(c, 0);   // 8 x 8 until a scene picks the automatic shape (ensure_tiles)
+    if (rc) return rc;
     // default camera (ogl_path_trace.h:53-54)
     const float defcam[12] = {0, -6, 1, 0, 0, 1, 0, 0, 0, 0, 0, 0};
     pt_set_camera(c, defcam);
@@ -295,24 +181,14 @@ void pt_destroy(pt_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     drop_graph(c);
     free_scene(c);
-    (void)hipFree(c->accum); (void)hipFree(c->rgba8); (void)hipFree(c->d_counters); (void)hipFree(c->d_work);
-    (void)hipFree(c->d_frame);
-    (void)hipFree(c->moments);
-    (void)hipFree(c->d_noise);
+    free_tiles(c);
+    void* const bufs[] = {c->accum, c->d_work, c->d_frame, c->d_rgb, c->moments, c->d_noise, c->d_adapt, c->dn_guide[0],
+                          c->dn_guide[1], c->dn_state[0], c->dn_state[1], c->dn_out, c->dn_rgba8, c->rgba8, c->d_counters};
+    for (void* b : bufs) (void)hipFree(b);
     if (c->h_noise) (void)hipHostFree(c->h_noise);
-    (void)hipFree(c->d_tile_perm);
-    (void)hipFree(c->d_tile_cost);
-    (void)hipFree(c->d_tile_frames);
-    (void)hipFree(c->d_active[0]);
-    (void)hipFree(c->d_active[1]);
-    (void)hipFree(c->d_adapt);
     if (c->h_adapt) (void)hipHostFree(c->h_adapt);
-    (void)hipFree(c->dn_guide[0]); (void)hipFree(c->dn_guide[1]);
-    (void)hipFree(c->dn_state[0]); (void)hipFree(c->dn_state[1]);
-    (void)hipFree(c->dn_out); (void)hipFree(c->dn_rgba8);
     for (hipEvent_t e : c->dn_ev)
         if (e) (void)hipEventDestroy(e);
-    (void)hipFree(c->d_rgb);
     for (int i = 0; i < kMaxSlots; i++) {
         if (c->rstream[i]) (void)hipStreamSynchronize(c->rstream[i]);
         if (c->rstream[i]) (void)hipStreamDestroy(c->rstream[i]);
@@ -356,11 +232,7 @@ int pt_upload_scene(pt_ctx* c, const float* tris, int n_tris, const float* bvh, 
         HIPCHK(c, hipMemcpy(c->d_scene[b], packed.buf[b].data(), bytes, hipMemcpyHostToDevice));
     }
     c->sf = packed.facts;
-    c->order_sorted = false;      // the next sort pools the new scene's first short launches
-    c->order_skip = 0;
-    c->n_sorts = 0;
     c->scene_ok = true;
-    c->guides_ok = false;         // the guides are of the old scene
     return PT_OK;
 }
 
@@ -502,21 +374,6 @@ int pt_set_tuning(pt_ctx* c, int key, int value) {
     return PT_OK;
 }
 
-// The work queue's tile shape (set_tiles): tuning key 20, else 8 x 8.  16 x 4 tiles for scenes
-// staged in LDS measured equal: with the builds in alternating order (ABBA, profiles/ab/
-// r06n_*) 16 x 4 and 8 x 8 are within 0.1% on C2 and C5; the +0.4..0.6% of the first A/Bs
-// (r06k_*, r06l_*, r06m_*) was tools/ab_inproc.py's first-position bias.  A shape change drains
-// the context's streams and drops a captured graph (which holds the tile arrays).
-static int ensure_tiles(pt_ctx* c) {
-    const int want = c->tile_key ? c->tile_key - 1 : 0;
-    if (want == c->tile_shift) return PT_OK;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int i = 0; i < kMaxSlots; i++)
-        if (c->rstream[i]) HIPCHK(c, hipStreamSynchronize(c->rstream[i]));
-    drop_graph(c);
-    return set_tiles(c, want);
-}
-
 constexpr int kOrderEvery = 64;               // short launches per tile-order sort (enqueue_render)
 constexpr int kOrderFirst = 8;                // ... and before the first sort after an upload
 constexpr int kProbeFrames = 2, kProbeMin = 64;  // cold long renders: a sorted order after 2 frames
@@ -562,9 +419,7 @@ static int ensure_slot(pt_ctx* c, int sl, int e, size_t need) {
         HIPCHK(c, hipMemset(c->d_work + kQueueSet * (1 + e), 0, kQueueSet * sizeof(unsigned)));
     }
     if (need <= c->slot_rgb_bytes[e]) return PT_OK;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int i = 0; i < kMaxSlots; i++)
-        if (c->rstream[i]) HIPCHK(c, hipStreamSynchronize(c->rstream[i]));
+    HIPCHK(c, drain_streams(c));
     (void)hipFree(c->slot_rgb[e]);
     c->slot_rgb[e] = nullptr;
     c->slot_rgb_bytes[e] = 0;
@@ -624,10 +479,10 @@ static void fill_image(KParams& p, const pt_ctx* c) {
     p.y_limit = (c->cfg.flags & PT_FLAG_REF_DISPATCH) ? (p.H / 10) * 10 : p.H;
 }
 
-// The kernel parameters of a launch, from the context and its plan (scratch, queue head and
-// the accumulate pass's outputs are the caller's).
-static KParams fill_params(const pt_ctx* c, const ptl::LaunchPlan& pl, int frame_first, int n_frames, int acc_first,
-                           const int* frame_dev, int frame_offset) {
+// The kernel parameters of a launch, from the context, the state it was planned with and its plan (scratch, queue
+// head and the accumulate pass's outputs are the caller's).
+static KParams fill_params(const pt_ctx* c, const ptl::LaunchPlan& pl, const ptl::State& st, int frame_first, int n_frames,
+                           int acc_first, const int* frame_dev, int frame_offset) {
     KParams p;
     std::memset(&p, 0, sizeof(p));
     // the wide walk reads the node / triangle arrays numbered by its index, and its records
@@ -649,7 +504,7 @@ static KParams fill_params(const pt_ctx* c, const ptl::LaunchPlan& pl, int frame
     p.n_slots = c->sf.n_slots, p.walk_np = c->sf.walk_np, p.n_mats = c->sf.n_mats, p.scene_fast = c->sf.scene_fast;
     std::memcpy(p.cons_m, c->sf.cons_m, sizeof(p.cons_m));
     std::memcpy(p.win_slack, c->sf.win_slack, sizeof(p.win_slack));
-    p.win_lo = ptl::window_cull_on(c->sf, c->tun, c->cfg.flags, c->counting) ? ptc::kWindowLo : -__builtin_huge_valf();
+    p.win_lo = ptl::window_cull_on(c->sf, c->tun, c->cfg.flags, st.counting) ? ptc::kWindowLo : -__builtin_huge_valf();
     std::memcpy(p.root_box, c->sf.root_box, sizeof(p.root_box));
     p.root_child = c->sf.root_child;
     // the plan
@@ -666,8 +521,46 @@ static KParams fill_params(const pt_ctx* c, const ptl::LaunchPlan& pl, int frame
     p.group = pl.group, p.pull_batch = pl.pull_batch, p.grp_magic = pl.grp_magic;
     p.tile_perm = c->d_tile_perm, p.tile_shift = c->tile_shift;
     p.queue_tiles = (unsigned)c->n_tiles;
-    p.tile_cost = (c->tun.adaptive && !c->counting) ? c->d_tile_cost : nullptr;
+    p.tile_cost = (c->tun.adaptive && !st.counting) ? c->d_tile_cost : nullptr;
     return p;
+}
+
+// One render launch on stream `rs`, the sequence every caller shares: the kernel of the plan's key (k_render_pool
+// for `pool`) with the plan's grid, block and LDS bytes, behind the reset of its queue head p.work_counter (an overlap
+// slot's was zeroed by its last accumulate pass).  `visible`: it shows in pt_debug_sweep, _pool and _launches.
+static int launch_render(pt_ctx* c, const ptl::LaunchPlan& pl, KParams& p, hipStream_t rs, bool common, bool pool, bool visible) {
+    // a sweeping launch has its table: the plan's `sweep` needs sweep_ok, and a scene with sweep_ok was packed with one
+    if (pl.sweep && (!p.sweep_tab || p.n_sweep < 1 || p.n_sweep > ptl::kSweepMaxLeaves || 2 * p.n_sweep != p.n_slots))
+        return fail(c, PT_E_STATE, "internal: a sweeping launch without a sweep table");
+    const RenderKernel* kernel = find_kernel(pl.key, common, pl.sweep);
+    if (visible) c->last_swept = pl.sweep, c->last_pooled = pool;
+    if (!kernel) {
+        const ptl::KernelKey& k = pl.key;
+        char key[96];
+        std::snprintf(key, sizeof key, "<%d,%d,%d,%d,%d,%d,%d,%d>", k.count, k.lds, k.minw, k.multi, k.split, k.padn, k.nt, k.wide);
+        return fail(c, PT_E_STATE, std::string("no k_render_sm instantiation for the launch key ") + key);
+    }
+    if (pl.overlap) p.reset_work = p.work_counter;
+    else HIPCHK(c, hipMemsetAsync(p.work_counter, 0, kQueueSet * sizeof(unsigned), rs));
+    if (pool)
+        hipLaunchKernelGGL((k_render_pool<ptl::kPoolThreads, ptl::kPoolPaths, ptl::kPoolWaves>), dim3(pl.pool_blocks),
+                           dim3((unsigned)pl.pool_nt), pl.pool_lds_bytes, rs, p);
+    else
+        hipLaunchKernelGGL(kernel->fn, dim3(pl.blocks), dim3((unsigned)kernel->key.nt), pl.dyn_lds_bytes, rs, p);
+    if (visible) c->n_line_launches[common]++;
+    return PT_OK;
+}
+
+// The plan and parameters of a launch that must be a plain split one on the context stream (an adaptive batch over
+// `im`'s tiles, a guide plane): planned with `st`, its full-image frame planes (aidx) in place as p.rgb.
+static int plan_plain_split(pt_ctx* c, const ptl::Image& im, const ptl::State& st, int frame_first, int n_frames,
+                            int acc_first, ptl::LaunchPlan& pl, KParams& p) {
+    pl = ptl::plan_launch(c->sf, c->tun, im, st, n_frames, false);
+    if (!pl.split || pl.overlap || pl.common) return fail(c, PT_E_STATE, "internal: not a plain split launch");
+    p = fill_params(c, pl, st, frame_first, n_frames, acc_first, nullptr, 0);
+    int rc = ensure_rgb(c, ptl::scratch_bytes(pl, plan_image(c), n_frames));
+    p.rgb = c->d_rgb;
+    return rc;
 }
 
 // Enqueues one render launch (work-queue reset + kernel) on the context stream.  With
@@ -676,10 +569,10 @@ static int enqueue_render(pt_ctx* c, int frame_first, int n_frames, int acc_firs
                           int frame_offset, bool force_sort = false) {
     c->stage_ok = false;    // this launch changes the image: rgba8 holds its view only if written below
     const ptl::LaunchPlan pl = plan(c, n_frames, frame_dev != nullptr);
-    KParams p = fill_params(c, pl, frame_first, n_frames, acc_first, frame_dev, frame_offset);
+    KParams p = fill_params(c, pl, plan_state(c), frame_first, n_frames, acc_first, frame_dev, frame_offset);
     // Overlapped short launches (the plan's `overlap`): the render kernel runs on overlap slot
     // `sl` (own stream, colour scratch and queue counter); the accumulate pass stays on the
-    // main stream, in frame order (the running mean, :548-551).  Dependencies: the slot's
+    // main stream, in frame order (the running mean, k_accum_frames).  Dependencies: the slot's
     // scratch is reused only after the accumulate pass that read it (ev_adone), and a render
     // never overlaps a tile-order sort (ev_fence; the sort runs on the main stream, which has
     // waited for every earlier render).
@@ -688,14 +581,12 @@ static int enqueue_render(pt_ctx* c, int frame_first, int n_frames, int acc_firs
     const int ring = kRingMult * c->tun.overlap_slots;
     const int re = c->ring % ring;       // this launch's scratch-ring entry
     hipStream_t rs = c->stream;
-    unsigned* work = c->d_work;
     if (pl.overlap) {
         int rc = ensure_slot(c, sl, re, scratch);
         if (rc) return rc;
         rs = c->rstream[sl];
-        work = c->d_work + kQueueSet * (1 + re);
         p.rgb = c->slot_rgb[re];
-        p.work_counter = work;
+        p.work_counter = c->d_work + kQueueSet * (1 + re);
         c->slot = (sl + 1) % c->tun.overlap_slots;
         c->ring = (re + 1) % ring;
     } else if (pl.split) {
@@ -705,35 +596,15 @@ static int enqueue_render(pt_ctx* c, int frame_first, int n_frames, int acc_firs
     }
     if (c->rows_local == 0) return PT_OK;
     const bool common = pl.common && common_params_ok(c, p, n_frames);
-    // a sweeping launch has its table: the plan's `sweep` needs sweep_ok, and a scene with sweep_ok was packed with one
-    if (pl.sweep && (!p.sweep_tab || p.n_sweep < 1 || p.n_sweep > ptl::kSweepMaxLeaves || 2 * p.n_sweep != p.n_slots))
-        return fail(c, PT_E_STATE, "internal: a sweeping launch without a sweep table");
-    const RenderKernel* kernel = find_kernel(pl.key, common, pl.sweep);
-    c->last_swept = pl.sweep;
     // the path pool: the plan's `pool` on the specialised swept line, and the bounce count its packing holds
     const bool pool = pl.pool && common && pl.sweep &&
                       ptpool::pack_ok(p.W, p.rows_local, n_frames, p.max_bounce, p.n_slots, p.sc.n_spheres);
-    c->last_pooled = pool;
-    if (!kernel) {
-        const ptl::KernelKey& k = pl.key;
-        char key[96];
-        std::snprintf(key, sizeof key, "<%d,%d,%d,%d,%d,%d,%d,%d>", k.count, k.lds, k.minw, k.multi, k.split, k.padn, k.nt, k.wide);
-        return fail(c, PT_E_STATE, std::string("no k_render_sm instantiation for the launch key ") + key);
-    }
     if (pl.overlap) {
         if (c->adone_rec[re]) HIPCHK(c, hipStreamWaitEvent(rs, c->ev_adone[re], 0));
         if (c->fence_rec) HIPCHK(c, hipStreamWaitEvent(rs, c->ev_fence, 0));
     }
-    // an overlap slot's heads were zeroed by the accumulate pass of its last render (or at
-    // the slot's creation)
-    if (pl.overlap) p.reset_work = work;
-    else HIPCHK(c, hipMemsetAsync(work, 0, kQueueSet * sizeof(unsigned), rs));
-    if (pool)
-        hipLaunchKernelGGL((k_render_pool<ptl::kPoolThreads, ptl::kPoolPaths, ptl::kPoolWaves>), dim3(pl.pool_blocks),
-                           dim3((unsigned)pl.pool_nt), pl.pool_lds_bytes, rs, p);
-    else
-        hipLaunchKernelGGL(kernel->fn, dim3(pl.blocks), dim3((unsigned)kernel->key.nt), pl.dyn_lds_bytes, rs, p);
-    c->n_line_launches[common]++;
+    const int rc = launch_render(c, pl, p, rs, common, pool, true);
+    if (rc) return rc;
     if (pl.split) {
         if (pl.overlap) {
             HIPCHK(c, hipEventRecord(c->ev_rdone[re], rs));
@@ -820,13 +691,11 @@ int pt_render_async(pt_ctx* c, int frame_first, int n_frames, int acc_first) {
     if (!c->scene_ok) return fail(c, PT_E_STATE, "pt_render before pt_upload_scene");
     if (n_frames <= 0) return fail(c, PT_E_ARG, "n_frames must be > 0");
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    {
-        int rc0 = ensure_tiles(c);
-        if (rc0) return rc0;
-    }
-    if (c->counting) HIPCHK(c, hipMemsetAsync(c->d_counters, 0, 16 * sizeof(unsigned long long), c->stream));
+    int rc = ensure_tiles(c);
+    if (rc) return rc;
+    HIPCHK(c, reset_counters(c));
     hipEvent_t ev[2];
-    int rc = take_events(c, ev);
+    rc = take_events(c, ev);
     if (rc) return rc;
     HIPCHK(c, hipEventRecord(ev[0], c->stream));
     // a caller that presented after its previous render gets the ACES view from this render's
@@ -867,18 +736,14 @@ int pt_progressive_setup(pt_ctx* c, int frames_per_launch, int launches_per_repl
     HIPCHK(c, hipSetDevice(c->cfg.device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     drop_graph(c);
-    {
-        int rc0 = ensure_tiles(c);
-        if (rc0) return rc0;
-    }
+    int rc = ensure_tiles(c);
+    if (rc) return rc;
     if (!c->d_frame) HIPCHK(c, hipMalloc(&c->d_frame, 64));
-    {   // no allocation inside the capture: the scratch of the largest sub-launch first
-        int rc0 = ensure_scratch(c, launch_frames(c, frames_per_launch), true);
-        if (rc0) return rc0;
-    }
+    // no allocation inside the capture: the scratch of the largest sub-launch first
+    rc = ensure_scratch(c, launch_frames(c, frames_per_launch), true);
+    if (rc) return rc;
     HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
     const unsigned long long sorts_before = c->n_sorts;   // captured sorts run (and count) per replay
-    int rc = PT_OK;
     for (int i = 0; i < launches_per_replay && rc == PT_OK; i++)
         rc = enqueue_frames(c, 0, frames_per_launch, 0, c->d_frame, i * frames_per_launch);
     if (rc == PT_OK) {
@@ -918,10 +783,8 @@ int pt_progressive_run(pt_ctx* c, int replays) {
     if (replays <= 0) return fail(c, PT_E_ARG, "replays must be > 0");
     HIPCHK(c, hipSetDevice(c->cfg.device));
     hipEvent_t ev[2];
-    {
-        int rc = take_events(c, ev);
-        if (rc) return rc;
-    }
+    const int rc = take_events(c, ev);
+    if (rc) return rc;
     HIPCHK(c, hipEventRecord(ev[0], c->stream));
     for (int r = 0; r < replays; r++) {
         HIPCHK(c, hipGraphLaunch(c->graph_exec, c->stream));
@@ -956,9 +819,8 @@ int pt_sync(pt_ctx* c) {
 }
 
 int pt_render(pt_ctx* c, int frame_first, int n_frames, int acc_first) {
-    int rc = pt_render_async(c, frame_first, n_frames, acc_first);
-    if (rc) return rc;
-    return pt_sync(c);
+    const int rc = pt_render_async(c, frame_first, n_frames, acc_first);
+    return rc ? rc : pt_sync(c);
 }
 
 int pt_rows(const pt_ctx* c, int* rows_local, int* row0, int* row_stride) {
@@ -995,10 +857,6 @@ int pt__scene_replicate_layout(pt_ctx* dst, const pt_ctx* src, void* dptr[ptp::k
         dptr[i] = dst->d_scene[i];
     }
     dst->sf = src->sf;
-    dst->order_sorted = false;
-    dst->order_skip = 0;
-    dst->n_sorts = 0;
-    dst->guides_ok = false;
     // scene_ok stays false until the caller has filled the buffers (pt__scene_set_ready): a
     // failed broadcast or copy must not leave a context rendering from uninitialised memory
     dst->scene_ok = false;
@@ -1010,8 +868,7 @@ int pt__scene_replicate_layout(pt_ctx* dst, const pt_ctx* src, void* dptr[ptp::k
 int pt__aces_launch(const void* src, void* dst, long long n, void* stream) {
     if (!src || !dst || n < 0) return PT_E_ARG;
     if (n == 0) return PT_OK;
-    hipLaunchKernelGGL(k_aces, dim3((unsigned)((n + 256 * kAcesPix - 1) / (256 * kAcesPix))), dim3(256), 0, (hipStream_t)stream,
-                       (const float4*)src, (uchar4*)dst, n);
+    launch_aces((hipStream_t)stream, (const float4*)src, (uchar4*)dst, n);
     return hipGetLastError() == hipSuccess ? PT_OK : PT_E_HIP;
 }
 
@@ -1039,642 +896,10 @@ int pt__query_view(const pt_ctx* c, ptq::CtxView* out) {
 }
 int pt__query_fail(pt_ctx* c, int code, const char* msg) { return fail(c, code, msg ? msg : ""); }
 
-int pt_read_rgba32f(pt_ctx* c, float* dst, size_t bytes) {
-    if (!c || !dst) return PT_E_ARG;
-    size_t need = (size_t)c->rows_local * c->cfg.width * sizeof(float4);
-    if (bytes < need) return fail(c, PT_E_ARG, "destination too small");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(dst, c->accum, need, hipMemcpyDeviceToHost));
-    return PT_OK;
-}
-
-int pt_write_rgba32f(pt_ctx* c, const float* src, size_t bytes) {
-    if (!c || !src) return PT_E_ARG;
-    c->stage_ok = false;
-    size_t need = (size_t)c->rows_local * c->cfg.width * sizeof(float4);
-    if (bytes < need) return fail(c, PT_E_ARG, "source too small");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(c->accum, src, need, hipMemcpyHostToDevice));
-    return PT_OK;
-}
-
-// The noise estimate.  Turning the moments on or off changes which accumulate
-// kernel every later launch runs and whether register-mode launches exist (split_mode), so
-// the context's streams are drained and a captured graph, which bakes the pointer in, is dropped.
-int pt_set_moments(pt_ctx* c, int enable) {
-    if (!c) return PT_E_ARG;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    const size_t px = std::max<size_t>((size_t)c->rows_local * c->cfg.width, 1);
-    c->mom_frames = 0;
-    c->mom_mixed = false;
-    if ((enable != 0) == (c->moments != nullptr)) {
-        // already so; on again: zeroed behind the passes that may still write them
-        if (c->moments) HIPCHK(c, hipMemsetAsync(c->moments, 0, px * sizeof(float2), c->stream));
-        return PT_OK;
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int i = 0; i < kMaxSlots; i++)
-        if (c->rstream[i]) HIPCHK(c, hipStreamSynchronize(c->rstream[i]));
-    drop_graph(c);
-    if (!enable) {
-        (void)hipFree(c->moments);
-        c->moments = nullptr;
-        return PT_OK;
-    }
-    if (!c->d_noise) HIPCHK(c, hipMalloc(&c->d_noise, sizeof(pt_noise_stats)));
-    if (!c->h_noise) HIPCHK(c, hipHostMalloc((void**)&c->h_noise, sizeof(pt_noise_stats), hipHostMallocDefault));
-    float2* m = nullptr;
-    HIPCHK(c, hipMalloc(&m, px * sizeof(float2)));
-    hipError_t e = hipMemset(m, 0, px * sizeof(float2));
-    if (e != hipSuccess) {
-        (void)hipFree(m);
-        return fail(c, PT_E_HIP, std::string("hipMemset(moments): ") + hipGetErrorString(e));
-    }
-    c->moments = m;
-    return PT_OK;
-}
-
-int pt_read_moments(pt_ctx* c, float* dst, size_t bytes, int* frames) {
-    if (!c || !dst) return PT_E_ARG;
-    if (!c->moments) return fail(c, PT_E_STATE, "moments are off (pt_set_moments)");
-    const size_t need = (size_t)c->rows_local * c->cfg.width * sizeof(float2);
-    if (bytes < need) return fail(c, PT_E_ARG, "destination too small");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(dst, c->moments, need, hipMemcpyDeviceToHost));
-    if (frames) *frames = c->mom_frames;
-    return PT_OK;
-}
-
-// The summary on the context stream, behind the accumulate passes it depends on: the 32-byte
-// block zeroed, k_noise, the block copied to pinned host memory; then one wait.
-int pt_noise(pt_ctx* c, float target, pt_noise_stats* out) {
-    if (!c || !out) return PT_E_ARG;
-    if (!c->moments) return fail(c, PT_E_STATE, "moments are off (pt_set_moments)");
-    if (c->mom_frames < 2) return fail(c, PT_E_STATE, "the noise estimate needs at least 2 frames");
-    if (c->mom_mixed) return fail(c, PT_E_STATE, "per-tile frame counts after pt_render_adaptive: no single n until the image restarts");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    HIPCHK(c, hipMemsetAsync(c->d_noise, 0, sizeof(pt_noise_stats), c->stream));
-    const long long px = (long long)c->rows_local * c->cfg.width;
-    if (px > 0) {
-        KParams p;
-        std::memset(&p, 0, sizeof(p));
-        fill_image(p, c);
-        p.moments = c->moments;
-        const unsigned blocks = (unsigned)std::min<long long>((px + 255) / 256, (long long)kNoiseBlocksPerCu * c->n_cu);
-        hipLaunchKernelGGL(k_noise, dim3(blocks), dim3(256), 0, c->stream, p, c->mom_frames, ptn::target_q(target),
-                           c->d_noise);
-        HIPCHK(c, hipGetLastError());
-    }
-    HIPCHK(c, hipMemcpyAsync(c->h_noise, c->d_noise, sizeof(pt_noise_stats), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *out = *c->h_noise;
-    out->frames = c->mom_frames;
-    return PT_OK;
-}
-
-int pt_render_until(pt_ctx* c, int frame_first, int acc_first, int batch, int max_frames, float target,
-                    int* frames_done, pt_noise_stats* last) {
-    if (!c || !frames_done) return PT_E_ARG;
-    *frames_done = 0;
-    if (batch < 2 || max_frames < batch || !(target > 0.0f))
-        return fail(c, PT_E_ARG, "pt_render_until: batch >= 2, max_frames >= batch, target > 0");
-    if (!c->scene_ok) return fail(c, PT_E_STATE, "pt_render_until before pt_upload_scene");
-    if (acc_first && c->moments && c->mom_mixed)
-        return fail(c, PT_E_STATE, "per-tile frame counts after pt_render_adaptive: pt_render_until must restart the image");
-    if (!c->moments) {
-        int rc = pt_set_moments(c, 1);
-        if (rc) return rc;
-    }
-    const unsigned long long tq = ptn::target_q(target);
-    pt_noise_stats s = {0, 0, 0, 0, 0};
-    int done = 0;
-    while (done < max_frames) {
-        const int n = std::min(batch, max_frames - done);
-        int rc = pt_render(c, frame_first + done, n, done ? 1 : acc_first);
-        if (rc) return rc;
-        done += n;
-        *frames_done = done;
-        rc = pt_noise(c, target, &s);
-        if (rc) return rc;
-        if (s.sum_q <= tq * s.pixels) break;      // mean relative error at or below the target
-    }
-    if (last) *last = s;
-    return PT_OK;
-}
-
-// Adaptive sampling.  The buffers of the tile grid, on first use after set_tiles.
-static int ensure_adaptive(pt_ctx* c) {
-    const size_t bytes = (size_t)std::max(c->n_tiles, 1) * sizeof(unsigned);
-    if (!c->d_adapt) HIPCHK(c, hipMalloc(&c->d_adapt, sizeof(AdaptSum)));
-    if (!c->h_adapt) HIPCHK(c, hipHostMalloc((void**)&c->h_adapt, sizeof(AdaptSum), hipHostMallocDefault));
-    if (!c->d_tile_frames) {
-        HIPCHK(c, hipMalloc(&c->d_tile_frames, bytes));
-        HIPCHK(c, hipMemsetAsync(c->d_tile_frames, 0, bytes, c->stream));
-    }
-    for (unsigned*& l : c->d_active)
-        if (!l) HIPCHK(c, hipMalloc(&l, bytes));
-    return PT_OK;
-}
-
-// One launch of an adaptive batch on the context stream: the render kernel over the `n_list` tiles of `list` (the
-// generic line of the key the planner gives for that many tiles, no tile costs), then k_accum_retire over the same
-// list.  n_after != 0: the batch's last launch, which decides.
-static int enqueue_adaptive(pt_ctx* c, int frame_first, int n_frames, int acc_first, const unsigned* list, unsigned n_list,
-                            unsigned* next, int n_after, unsigned frames_after, unsigned target_q) {
-    ptl::Image im = plan_image(c);
-    im.n_tiles = (int)n_list;
-    ptl::State st = plan_state(c);
-    st.adaptive = true;
-    const ptl::LaunchPlan pl = ptl::plan_launch(c->sf, c->tun, im, st, n_frames, false);
-    if (!pl.split || pl.overlap || pl.common) return fail(c, PT_E_STATE, "internal: an adaptive launch must be a plain split launch");
-    KParams p = fill_params(c, pl, frame_first, n_frames, acc_first, nullptr, 0);
-    int rc = ensure_rgb(c, ptl::scratch_bytes(pl, plan_image(c), n_frames));   // full-image planes (aidx)
-    if (rc) return rc;
-    p.rgb = c->d_rgb;
-    p.tile_perm = list;
-    p.queue_tiles = n_list;
-    p.tile_cost = nullptr;
-    p.moments = c->moments;
-    if (pl.sweep && (!p.sweep_tab || p.n_sweep < 1 || p.n_sweep > ptl::kSweepMaxLeaves || 2 * p.n_sweep != p.n_slots))
-        return fail(c, PT_E_STATE, "internal: a sweeping launch without a sweep table");
-    const RenderKernel* kernel = find_kernel(pl.key, false, false);
-    if (!kernel) return fail(c, PT_E_STATE, "no k_render_sm instantiation for the adaptive launch's key");
-    c->last_swept = pl.sweep;
-    c->last_pooled = false;
-    HIPCHK(c, hipMemsetAsync(c->d_work, 0, kQueueSet * sizeof(unsigned), c->stream));
-    hipLaunchKernelGGL(kernel->fn, dim3(pl.blocks), dim3((unsigned)kernel->key.nt), pl.dyn_lds_bytes, c->stream, p);
-    c->n_line_launches[0]++;
-    const unsigned per_wave = adapt_tiles_per_wave(n_list), per_block = 4u * per_wave;
-    AdaptArgs a = {n_list, per_wave, c->n_tiles, n_after, frames_after, target_q, c->d_tile_frames, next, c->d_adapt};
-    hipLaunchKernelGGL(k_accum_retire, dim3((n_list + per_block - 1) / per_block), dim3(256), 0, c->stream, p, a);
-    HIPCHK(c, hipGetLastError());
-    return PT_OK;
-}
-
-int pt_render_adaptive(pt_ctx* c, int frame_first, int acc_first, int batch, int max_frames, float target,
-                       int* frames_done, pt_adaptive_stats* last) {
-    if (!c || !frames_done) return PT_E_ARG;
-    *frames_done = 0;
-    if (batch < 2 || max_frames < batch || !(target > 0.0f))
-        return fail(c, PT_E_ARG, "pt_render_adaptive: batch >= 2, max_frames >= batch, target > 0");
-    if (!c->scene_ok) return fail(c, PT_E_STATE, "pt_render_adaptive before pt_upload_scene");
-    if (acc_first && c->moments && c->mom_mixed)
-        return fail(c, PT_E_STATE, "per-tile frame counts after pt_render_adaptive: the next adaptive call must restart the image");
-    if (!c->moments) {
-        int rc = pt_set_moments(c, 1);
-        if (rc) return rc;
-    }
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    int rc = ensure_tiles(c);
-    if (rc) return rc;
-    rc = ensure_adaptive(c);
-    if (rc) return rc;
-    const int n0 = acc_first ? c->mom_frames : 0;
-    const unsigned tq = ptn::target_q(target);
-    const size_t tile_bytes = (size_t)std::max(c->n_tiles, 1) * sizeof(unsigned);
-    if (c->counting) HIPCHK(c, hipMemsetAsync(c->d_counters, 0, 16 * sizeof(unsigned long long), c->stream));
-    c->stage_ok = false;
-    c->aces_fuse = false;       // no ACES view from these passes: pt_present_begin runs its own
-    c->presented = false;
-    // the first list: every tile, in the learned order (behind the sorts on this stream; overlapped renders of
-    // earlier calls have been waited for by the accumulate passes on it)
-    HIPCHK(c, hipMemcpyAsync(c->d_active[0], c->d_tile_perm, tile_bytes, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_tile_frames, 0, tile_bytes, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_adapt, 0, sizeof(AdaptSum), c->stream));
-    std::memset(c->h_adapt, 0, sizeof(AdaptSum));
-    unsigned n_list = c->rows_local > 0 ? (unsigned)c->n_tiles : 0u;
-    int done = 0, cur = 0;
-    while (done < max_frames && n_list > 0) {
-        const int n = std::min(batch, max_frames - done);
-        // the batch's share of the summary block: the tiles that stay active, and the next list's length
-        HIPCHK(c, hipMemsetAsync(&c->d_adapt->act_pixels, 0, sizeof(AdaptSum) - offsetof(AdaptSum, act_pixels), c->stream));
-        // a batch too large for the scratch budget or the 32-bit queue ids runs as several launches; the last decides
-        const int step = launch_frames(c, n);
-        for (int off = 0; off < n; off += step) {
-            const int m = std::min(step, n - off);
-            const bool decides = off + m >= n;
-            rc = enqueue_adaptive(c, frame_first + done + off, m, (done + off) ? 1 : acc_first, c->d_active[cur], n_list,
-                                  c->d_active[cur ^ 1], decides ? n0 + done + n : 0, (unsigned)(done + n), tq);
-            if (rc) return rc;
-        }
-        HIPCHK(c, hipMemcpyAsync(c->h_adapt, c->d_adapt, sizeof(AdaptSum), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        done += n;
-        c->mom_frames = n0 + done;      // the largest count; per tile from here on
-        c->mom_mixed = true;
-        c->adapt_done = done;
-        if (c->h_adapt->n_next > n_list) return fail(c, PT_E_STATE, "internal: the active list grew");
-        n_list = c->h_adapt->n_next;
-        cur ^= 1;
-    }
-    if (done == 0) {    // a context without rows: nothing rendered, the (empty) state restarts like the image
-        if (!acc_first) c->mom_frames = 0, c->mom_mixed = false;
-    }
-    c->count_pending = c->counting;
-    *frames_done = done;
-    if (last) {
-        const AdaptSum& s = *c->h_adapt;
-        last->noise.pixels = s.ret_pixels + s.act_pixels;
-        last->noise.sum_q = s.ret_sum_q + s.act_sum_q;
-        last->noise.above = s.ret_above + s.act_above;
-        last->noise.max_q = std::max(s.ret_max_q, s.act_max_q);
-        last->noise.frames = n0 + done;
-        last->tiles = s.ret_tiles + s.n_next;
-        last->tiles_active = s.n_next;
-        last->pixel_frames = s.pixel_frames;
-    }
-    return pt_sync(c);
-}
-
-int pt_read_tile_frames(pt_ctx* c, unsigned* dst, int max_tiles, int* n_tiles, int* tiles_x) {
-    if (!c) return PT_E_ARG;
-    if (dst && max_tiles < c->n_tiles) return fail(c, PT_E_ARG, "tile frame buffer too small");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (n_tiles) *n_tiles = c->n_tiles;
-    if (tiles_x) *tiles_x = c->tiles_x;
-    if (dst && c->n_tiles > 0) {
-        if (c->d_tile_frames)
-            HIPCHK(c, hipMemcpy(dst, c->d_tile_frames, (size_t)c->n_tiles * sizeof(unsigned), hipMemcpyDeviceToHost));
-        else
-            std::memset(dst, 0, (size_t)c->n_tiles * sizeof(unsigned));
-    }
-    return PT_OK;
-}
-
-// ---------------------------------------------------------------- denoised view
-// One launch of a guide render on the context stream: the render kernel in display mode `mode` over the whole tile
-// grid, then the plain accumulate pass into `plane` instead of the image.  Planned like an adaptive launch -- a
-// frame-split launch on the generic line of its key, on the context's own stream, never counting -- and invisible to
-// the context: no tile costs, no moments, no ACES view, no timing events, and none of the launch bookkeeping
-// (pt_debug_launches, pt_debug_sweep, pt_debug_pool, the sort cadence) moves.
-static int enqueue_guide(pt_ctx* c, const ptl::State& st, int mode, int frame_first, int n_frames, int acc_first, float4* plane) {
-    const ptl::Image im = plan_image(c);
-    const ptl::LaunchPlan pl = ptl::plan_launch(c->sf, c->tun, im, st, n_frames, false);
-    if (!pl.split || pl.overlap || pl.common) return fail(c, PT_E_STATE, "internal: a guide launch must be a plain split launch");
-    KParams p = fill_params(c, pl, frame_first, n_frames, acc_first, nullptr, 0);
-    int rc = ensure_rgb(c, ptl::scratch_bytes(pl, im, n_frames));
-    if (rc) return rc;
-    p.rgb = c->d_rgb;
-    p.accum = plane;
-    p.mode = mode;
-    p.tile_cost = nullptr;
-    p.moments = nullptr;
-    // (fill_params decides the window clause with the context's counting flag; a guide launch never counts)
-    p.win_lo = ptl::window_cull_on(c->sf, c->tun, c->cfg.flags, false) ? ptc::kWindowLo : -__builtin_huge_valf();
-    if (pl.sweep && (!p.sweep_tab || p.n_sweep < 1 || p.n_sweep > ptl::kSweepMaxLeaves || 2 * p.n_sweep != p.n_slots))
-        return fail(c, PT_E_STATE, "internal: a sweeping launch without a sweep table");
-    const RenderKernel* kernel = find_kernel(pl.key, false, false);
-    if (!kernel) return fail(c, PT_E_STATE, "no k_render_sm instantiation for the guide launch's key");
-    HIPCHK(c, hipMemsetAsync(c->d_work, 0, kQueueSet * sizeof(unsigned), c->stream));
-    hipLaunchKernelGGL(kernel->fn, dim3(pl.blocks), dim3((unsigned)kernel->key.nt), pl.dyn_lds_bytes, c->stream, p);
-    const KParamsKernel acc = pl.accum_long ? k_accum_frames<kAccumPixLong, kAccumFramesLong> : k_accum_frames<kAccumPix, 1>;
-    hipLaunchKernelGGL(acc, dim3(pl.accum_blocks), dim3(256), 0, c->stream, p);
-    HIPCHK(c, hipGetLastError());
-    return PT_OK;
-}
-
-// The guide planes of `frames` frames: display modes 2, 3 and 4 rendered as pt_render(1, frames, 0) would, each into a
-// zeroed plane (pixels outside the dispatch footprint stay zero), then packed.
-static int render_guides(pt_ctx* c, int frames) {
-    const size_t bytes = (size_t)c->rows_local * c->cfg.width * sizeof(float4);
-    float4* raw[3] = {c->dn_state[0], c->dn_state[1], c->dn_out};
-    ptl::State st = {false, true, false};   // not counting; split as with the moments on (the pass below keeps none)
-    st.adaptive = true;
-    for (int m = 0; m < 3; m++) {
-        HIPCHK(c, hipMemsetAsync(raw[m], 0, bytes, c->stream));
-        int done = 0;
-        while (done < frames) {
-            const int n = ptl::launch_frames(c->sf, c->tun, plan_image(c), st, frames - done);
-            int rc = enqueue_guide(c, st, 2 + m, 1 + done, n, done ? 1 : 0, raw[m]);
-            if (rc) return rc;
-            done += n;
-        }
-    }
-    ptd::launch_pack(c->stream, raw[0], raw[1], raw[2], c->dn_guide[0], c->dn_guide[1],
-                     (long long)c->rows_local * c->cfg.width);
-    HIPCHK(c, hipGetLastError());
-    return PT_OK;
-}
-
-int pt_denoise_async(pt_ctx* c, const pt_denoise_params* params, pt_denoise_info* info) {
-    if (!c) return PT_E_ARG;
-    pt_denoise_params dp;
-    pt_denoise_defaults(&dp);
-    if (params) dp = *params;
-    if (dp.iterations < 1 || dp.iterations > ptd::kMaxIterations) return fail(c, PT_E_ARG, "pt_denoise: iterations must be 1..8");
-    if (dp.guide_frames < 1) return fail(c, PT_E_ARG, "pt_denoise: guide_frames must be >= 1");
-    if (!c->scene_ok) return fail(c, PT_E_STATE, "pt_denoise before pt_upload_scene");
-    if (c->cfg.world > 1)
-        return fail(c, PT_E_STATE, "pt_denoise on a row-split context: its interleaved rows have no neighbours (groups are out of scope)");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    const size_t px = (size_t)c->rows_local * c->cfg.width;     // world == 1: every row
-    if (!c->dn_out) {
-        float4** planes[5] = {&c->dn_guide[0], &c->dn_guide[1], &c->dn_state[0], &c->dn_state[1], &c->dn_out};
-        for (float4** pl : planes)
-            if (!*pl) HIPCHK(c, hipMalloc(pl, px * sizeof(float4)));
-    }
-    if (c->dn_timing)
-        for (hipEvent_t& e : c->dn_ev)
-            if (!e) HIPCHK(c, hipEventCreate(&e));
-    int ev = 0;
-    const auto mark = [&]() { if (c->dn_timing) (void)hipEventRecord(c->dn_ev[ev++], c->stream); };
-    mark();
-    const bool render = !c->guides_ok || c->guides_frames != dp.guide_frames;
-    if (render) {
-        c->guides_ok = false;
-        c->dn_done = false;     // (the rendered planes pass through the result's plane)
-        int rc = render_guides(c, dp.guide_frames);
-        if (rc) return rc;
-        c->guides_ok = true;
-        c->guides_frames = dp.guide_frames;
-    }
-    mark();
-    const bool guided = c->moments != nullptr && c->mom_frames >= 2;
-    ptd::Image im;
-    {
-        KParams p;
-        fill_image(p, c);
-        im = {p.W, p.H, p.x_limit, p.y_limit};
-    }
-    const bool per_tile = guided && c->mom_mixed && c->d_tile_frames;
-    ptd::launch_prep(c->stream, im, c->accum, guided ? c->moments : nullptr, c->mom_frames,
-                     per_tile ? c->d_tile_frames : nullptr, c->mom_frames - c->adapt_done, c->tile_shift, c->tiles_x,
-                     c->dn_state[0]);
-    mark();
-    const ptd::K k = {ptd::inv_sq(dp.sigma_lum), ptd::inv_sq(dp.sigma_normal), ptd::inv_sq(dp.sigma_albedo),
-                      ptd::inv_sq(dp.sigma_depth)};
-    for (int i = 0; i < dp.iterations; i++) {
-        const bool last = i + 1 == dp.iterations;
-        ptd::launch_iter(c->stream, im, c->dn_state[i & 1], last ? c->dn_out : c->dn_state[(i + 1) & 1], c->dn_guide[0],
-                         c->dn_guide[1], last ? c->accum : nullptr, 1 << i, guided, k, c->dn_variant);
-        mark();
-    }
-    c->dn_ev_n = ev;
-    HIPCHK(c, hipGetLastError());
-    c->dn_done = true;
-    if (info) *info = {guided ? 1 : 0, render ? 1 : 0, dp.iterations, c->moments ? c->mom_frames : 0};
-    return PT_OK;
-}
-
-int pt_denoise(pt_ctx* c, const pt_denoise_params* params, pt_denoise_info* info) {
-    int rc = pt_denoise_async(c, params, info);
-    if (rc) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PT_OK;
-}
-
-int pt_read_denoised_rgba32f(pt_ctx* c, float* dst, size_t bytes) {
-    if (!c || !dst) return PT_E_ARG;
-    if (!c->dn_done) return fail(c, PT_E_STATE, "no denoised image (pt_denoise first)");
-    const size_t need = (size_t)c->rows_local * c->cfg.width * sizeof(float4);
-    if (bytes < need) return fail(c, PT_E_ARG, "destination too small");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(dst, c->dn_out, need, hipMemcpyDeviceToHost));
-    return PT_OK;
-}
-
-int pt_read_denoised_rgba8_aces(pt_ctx* c, unsigned char* dst, size_t bytes) {
-    if (!c || !dst) return PT_E_ARG;
-    if (!c->dn_done) return fail(c, PT_E_STATE, "no denoised image (pt_denoise first)");
-    const long long n = (long long)c->rows_local * c->cfg.width;
-    if (bytes < (size_t)n * 4) return fail(c, PT_E_ARG, "destination too small");
-    if (n == 0) return PT_OK;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    if (!c->dn_rgba8) HIPCHK(c, hipMalloc(&c->dn_rgba8, (size_t)n * sizeof(uchar4)));
-    // a view of its own: the image's (rgba8, stage_ok) is pt_present_*'s
-    hipLaunchKernelGGL(k_aces, dim3((unsigned)((n + 256 * kAcesPix - 1) / (256 * kAcesPix))), dim3(256), 0, c->stream,
-                       c->dn_out, c->dn_rgba8, n);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(dst, c->dn_rgba8, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return PT_OK;
-}
-
-int pt_read_guides(pt_ctx* c, float* dst, size_t bytes) {
-    if (!c || !dst) return PT_E_ARG;
-    if (!c->guides_ok) return fail(c, PT_E_STATE, "no guides (pt_denoise first)");
-    const size_t n = (size_t)c->rows_local * c->cfg.width;
-    if (bytes < n * 8 * sizeof(float)) return fail(c, PT_E_ARG, "destination too small");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::vector<float> g(n * 4);
-    for (int h = 0; h < 2; h++) {
-        if (n) HIPCHK(c, hipMemcpy(g.data(), c->dn_guide[h], n * sizeof(float4), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < n; i++) std::memcpy(dst + 8 * i + 4 * h, g.data() + 4 * i, 4 * sizeof(float));
-    }
-    return PT_OK;
-}
-
-// Measurements only (tools/denoise_measure.py; not part of the public ABI): how the iterations read their taps
-// (ptd::Variant), and events around the guide render, the prep and each iteration of the denoises that follow.
-int pt__denoise_debug(pt_ctx* c, int variant, int timing) {
-    if (!c || variant < 0 || variant > 1) return PT_E_ARG;
-    c->dn_variant = variant;
-    c->dn_timing = timing != 0;
-    c->dn_ev_n = 0;
-    return PT_OK;
-}
-// ms of the last timed denoise: out[0] guide render, [1] prep, [2 ..] the iterations; returns the count (waits).
-int pt__denoise_times(pt_ctx* c, float* out, int max_out) {
-    if (!c || !out) return PT_E_ARG;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    int n = 0;
-    for (int i = 0; i + 1 < c->dn_ev_n && n < max_out; i++, n++) HIPCHK(c, hipEventElapsedTime(&out[n], c->dn_ev[i], c->dn_ev[i + 1]));
-    return n;
-}
-
-int pt_read_rgba8_aces(pt_ctx* c, unsigned char* dst, size_t bytes) {
-    if (!c || !dst) return PT_E_ARG;
-    long long n = (long long)c->rows_local * c->cfg.width;
-    if (bytes < (size_t)n * 4) return fail(c, PT_E_ARG, "destination too small");
-    if (n == 0) return PT_OK;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    // the view the last render's accumulate pass wrote when the caller also read (or presented)
-    // after the render before it (pt_present_begin), else the ACES pass here
-    if (!c->stage_ok) {
-        hipLaunchKernelGGL(k_aces, dim3((unsigned)((n + 256 * kAcesPix - 1) / (256 * kAcesPix))), dim3(256), 0,
-                           c->stream, c->accum, c->rgba8, n);
-        HIPCHK(c, hipGetLastError());
-    }
-    c->stage_ok = true;     // rgba8 is the view of the current image
-    c->presented = true;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(dst, c->rgba8, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return PT_OK;
-}
-
-// Asynchronous presentation for a viewer that shows every frame (ogl_path_trace.h:189-192
-// draws each frame's texture on the GPU that rendered it; a headless caller reads it back).
-// begin: the ACES epilogue of the current image on the context stream (after every render
-// issued so far and its running mean), then a copy into pinned host memory on a separate
-// stream, so renders issued after it run while the image crosses PCIe.  end: waits for that
-// copy and hands out the pinned pixels.
-int pt_present_begin(pt_ctx* c, int buf) {
-    if (!c) return PT_E_ARG;
-    if (buf < 0 || buf >= kPresentBufs) return fail(c, PT_E_ARG, "present buffer must be 0..3");
-    const long long n = (long long)c->rows_local * c->cfg.width;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    if (!c->present_host[buf]) {
-        HIPCHK(c, hipHostMalloc((void**)&c->present_host[buf], std::max<long long>(n, 1) * sizeof(uchar4),
-                                hipHostMallocDefault));
-        HIPCHK(c, hipEventCreateWithFlags(&c->ev_copied[buf], hipEventDisableTiming));
-    }
-    // a buffer begun again before its end: its previous copy must land first
-    if (c->present_pending[buf]) HIPCHK(c, hipEventSynchronize(c->ev_copied[buf]));
-    c->present_pending[buf] = false;
-    // the view of the current image: written by the last render's accumulate pass when the
-    // caller presented after the render before it (stage_ok), else the ACES pass here
-    if (n > 0 && !c->stage_ok) {
-        hipLaunchKernelGGL(k_aces, dim3((unsigned)((n + 256 * kAcesPix - 1) / (256 * kAcesPix))), dim3(256), 0,
-                           c->stream, c->accum, c->rgba8, n);
-        HIPCHK(c, hipGetLastError());
-    }
-    c->stage_ok = true;     // rgba8 is the view of the current image
-    c->presented = true;
-    // the copy on the context stream itself: a copy stream waiting on an event started each
-    // copy about 150 us after the view was ready (one-frame loop with lag 2: 0.578 -> 0.537
-    // ms per frame); the next render's accumulate pass, which rewrites the view, follows it
-    if (n > 0)
-        HIPCHK(c, hipMemcpyAsync(c->present_host[buf], c->rgba8, (size_t)n * sizeof(uchar4), hipMemcpyDeviceToHost,
-                                 c->stream));
-    HIPCHK(c, hipEventRecord(c->ev_copied[buf], c->stream));
-    c->present_pending[buf] = true;
-    return PT_OK;
-}
-
-int pt_present_end(pt_ctx* c, int buf, const unsigned char** pixels) {
-    if (!c || !pixels) return PT_E_ARG;
-    if (buf < 0 || buf >= kPresentBufs) return fail(c, PT_E_ARG, "present buffer must be 0..3");
-    if (!c->present_pending[buf]) return fail(c, PT_E_STATE, "pt_present_end without pt_present_begin");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    HIPCHK(c, hipEventSynchronize(c->ev_copied[buf]));
-    c->present_pending[buf] = false;
-    *pixels = c->present_host[buf];
-    return PT_OK;
-}
-
-int pt_accum_device(pt_ctx* c, void** ptr, size_t* bytes) {
-    if (!c) return PT_E_ARG;
-    c->stage_ok = false;   // the caller may write the image through this pointer
-    if (ptr) *ptr = c->accum;
-    if (bytes) *bytes = (size_t)c->rows_local * c->cfg.width * sizeof(float4);
-    return PT_OK;
-}
-
-int pt_copy_rows_device(pt_ctx* c, void* dst, size_t bytes) {
-    if (!c || !dst) return PT_E_ARG;
-    size_t need = (size_t)c->rows_local * c->cfg.width * sizeof(float4);
-    if (bytes < need) return fail(c, PT_E_ARG, "destination too small");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    HIPCHK(c, hipMemcpyAsync(dst, c->accum, need, hipMemcpyDeviceToDevice, c->stream));
-    return pt_sync(c);
-}
-
-int pt_timing(pt_ctx* c, double* total_ms, int* n, int reset) {
-    if (!c) return PT_E_ARG;
-    if (total_ms) *total_ms = c->total_ms;
-    if (n) *n = c->n_launches;
-    if (reset) { c->total_ms = 0.0; c->n_launches = 0; }
-    return PT_OK;
-}
-
-int pt_stream(pt_ctx* c, void** s) {
-    if (!c || !s) return PT_E_ARG;
-    c->stage_ok = false;   // ... or queue work on this stream that does
-    *s = (void*)c->stream;
-    return PT_OK;
-}
-
-#ifdef PT_WAVE_TRACE
-extern "C" int pt_debug_wave_trace(unsigned long long* out, int max_waves, int reset) {
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    const int n = max_waves < kWaveTraceMax ? max_waves : kWaveTraceMax;
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wave_trace), sizeof(unsigned long long) * 4 * n) != hipSuccess) return -1;
-    if (reset) {
-        std::vector<unsigned long long> z(4 * (size_t)kWaveTraceMax, 0ull);
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_wave_trace), z.data(), z.size() * 8) != hipSuccess) return -1;
-    }
-    return n;
-}
-#endif
-
-#ifdef PT_PHASE_CLOCK
-extern "C" int pt_debug_phase_clock(unsigned long long out[8], int reset) {
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_phase_clk), sizeof(unsigned long long) * 8) != hipSuccess) return -1;
-    if (reset) {
-        unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_phase_clk), z, sizeof(z)) != hipSuccess) return -1;
-    }
-    return 0;
-}
-#endif
-
-
-int pt_stats_ex(pt_ctx* c, unsigned long long out[16]) {
-    if (!c || !out) return PT_E_ARG;
-    std::memcpy(out, c->last_counts, sizeof(c->last_counts));
-    out[13] = c->sf.lds_bytes;
-    out[14] = c->sf.walk_nested ? c->sf.lds_bytes_sk : 0;
-    out[15] = ptl::cons_walk_on(c->sf, c->tun, c->counting);               // the scene's LDS walk culls (slab_oct_cons)
-    return PT_OK;
-}
-
-int pt_debug_window_cull(pt_ctx* c, int* active, float* slack) {
-    if (!c) return PT_E_ARG;
-    if (active) *active = ptl::window_cull_on(c->sf, c->tun, c->cfg.flags, c->counting) ? 1 : 0;
-    if (slack) *slack = std::max(c->sf.win_slack[0], std::max(c->sf.win_slack[1], c->sf.win_slack[2]));
-    return PT_OK;
-}
-
-int pt_debug_sweep(pt_ctx* c, int* swept, int* qualifies, int* n_leaves) {
-    if (!c) return PT_E_ARG;
-    if (swept) *swept = c->last_swept ? 1 : 0;
-    if (qualifies) *qualifies = c->sf.sweep_ok ? 1 : 0;
-    if (n_leaves) *n_leaves = c->sf.n_leaves;
-    return PT_OK;
-}
-
-int pt_debug_pool(pt_ctx* c, int* pooled) {
-    if (!c) return PT_E_ARG;
-    if (pooled) *pooled = c->last_pooled ? 1 : 0;
-    return PT_OK;
-}
-
-int pt_debug_launches(pt_ctx* c, unsigned long long out[2]) {
-    if (!c || !out) return PT_E_ARG;
-    out[0] = c->n_line_launches[0];
-    out[1] = c->n_line_launches[1];
-    return PT_OK;
-}
-
-int pt_debug_tile_order(pt_ctx* c, unsigned long long* sorts, unsigned* perm_out, int max_tiles, int* n_tiles,
-                        int* tiles_x) {
-    if (!c) return PT_E_ARG;
-    if (perm_out && max_tiles < c->n_tiles) return fail(c, PT_E_ARG, "tile order buffer too small");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    // the sorts run on the context stream, which waits for every render before them
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (sorts) *sorts = c->n_sorts;
-    if (n_tiles) *n_tiles = c->n_tiles;
-    if (tiles_x) *tiles_x = c->tiles_x;
-    if (perm_out && c->n_tiles > 0)
-        HIPCHK(c, hipMemcpy(perm_out, c->d_tile_perm, (size_t)c->n_tiles * sizeof(unsigned), hipMemcpyDeviceToHost));
-    return PT_OK;
-}
-
-int pt_stats(pt_ctx* c, double* ms, unsigned long long out[5]) {
-    if (!c) return PT_E_ARG;
-    if (ms) *ms = c->last_ms;
-    if (out) std::memcpy(out, c->last_counts, 5 * sizeof(unsigned long long));
-    return PT_OK;
-}
-
 }  // extern "C"
 
+// The rest of the host half, as sections of this translation unit (each opens its own extern "C"):
+#include "pt_ctx_noise.h"      // the moments, pt_noise, pt_render_until, adaptive sampling
+#include "pt_ctx_denoise.h"    // the guide launch, pt_denoise*, the denoised reads
+#include "pt_ctx_io.h"         // reading and writing the image, the 8-bit view, pt_present_*, timing
+#include "pt_ctx_debug.h"      // pt_debug_*, pt_stats, pt_stats_ex

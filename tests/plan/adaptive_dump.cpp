@@ -1,6 +1,6 @@
 // adaptive_dump -- plan_dump for the launches of pt_render_adaptive: the same 40-integer cases on
 // stdin and the same "case | plan" lines, but planned with State::adaptive set, as
-// enqueue_adaptive (pt_render.hip) does, n_tiles being the launch's list of active tiles.  After
+// enqueue_adaptive (pt_ctx_noise.h) does, n_tiles being the launch's list of active tiles.  After
 // the plan_dump fields come `overlap` and `common` once more, named, for tests/test_adaptive_plan.py.
 #include "../../opengl-path-tracing_amd/csrc/pt_launch_plan.h"
 

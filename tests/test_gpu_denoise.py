@@ -53,6 +53,28 @@ def test_guides_cornell(cornell_scene, guide_frames):
     pt.close()
 
 
+def test_guides_counting_context(cornell_scene):
+    """A counting context: the guide launches never count (their window clause and kernel follow the launch's own
+    state, not the context's flag), so the guides are the oracle's and the counters stay those of the render."""
+    w, h = 32, 24
+
+    def counters():
+        v = np.zeros(16, np.uint64)
+        pt._check(H.lib().pt_stats_ex(pt.h, v))
+        return v
+
+    pt = tracer(cornell_scene, w, h)
+    pt.set_counting(True)
+    pt.render(1, 4, 0)
+    before = counters()
+    assert before[0] > 0, "the render counted nothing"
+    assert pt.denoise(guide_frames=2)["guides_rendered"]
+    same_bits(pt.read_guides(), oracle_guides(cornell_scene, w, h, 2), "guides on a counting context")
+    pt.sync()
+    assert np.array_equal(counters(), before)
+    pt.close()
+
+
 def test_guides_cache(cornell_scene):
     """Rendered by the first call, kept by the second; again after set_camera, upload and another guide_frames."""
     w, h = 40, 30
