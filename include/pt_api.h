@@ -430,6 +430,50 @@ int pt_intersect_host(const float* tris, int n_tris, const float* bvh, int n_nod
                       const float* spheres, int n_spheres, int ctx_flags, const pt_ray* rays, long long n,
                       pt_hit* hits, int query_flags);
 
+/* Traced rays: the light that arrives along a caller's ray -- cameras other than the built-in
+ * pinhole (panoramas, orthographic views, stereo pairs, a thin lens), light probes and lightmap baking, the radiance
+ * behind a picked pixel, an integrator the client drives itself.
+ *
+ * For ray i and frame f the random state is seeds[i] + (uint32)f * 719393u, wrapping, and rgb is the reference's
+ * Trace (computeShader.c:434-501) from o, d with that state: incoming light 0, ray colour 1, and for every segment up
+ * to the context's max_bounce one closest hit as pt_intersect finds it, then the surface bounce, the sky or a
+ * display-mode return as a render shades it.  d is used as given, not normalised; there are no jitter draws and no
+ * rays_per_pixel: the ray is the caller's.  The first segment's search starts at the ray's t_max, later segments at
+ * +inf; t_max = +inf is exactly the reference.  The context's max_bounce, display mode as last set, PT_FLAG_NO_SKY,
+ * PT_FLAG_NO_SPHERES, PT_FLAG_NO_TRIANGLES and PT_FLAG_MOLLER_TRUMBORE apply as in a render; PT_FLAG_NO_AA and
+ * PT_FLAG_REF_DISPATCH mean nothing here.  NaN or zero components get no special case and fall out of the IEEE
+ * arithmetic, as for a query.
+ *
+ * Frames frame_first .. frame_first + n_frames - 1 of a ray are folded into rgba[i] in frame order by the render's
+ * running mean: the first frame overwrites when accumulate_first = 0 (rgba is then never read) and averages over the
+ * caller's values when it is 1; every later frame averages.  This is pt_render's rule.
+ *
+ * Consequence: with rays from pt_pixel_rays and seeds from pt_pixel_seeds, pt_trace(.., F, N, A, rgba) writes the
+ * pixels of pt_render(F, N, A) on a PT_FLAG_NO_AA, one-ray-per-pixel context with that camera, bit for bit.
+ *
+ * Like a query, a trace is invisible to rendering: no timing events, launch counters, sweep or pool flags, tile
+ * order, moments, presented state or captured graph, and nothing written that a render reads.
+ *
+ * n rays from host arrays, synchronous; rgba holds n * 4 floats, in and out.  seeds = NULL: seeds[i] =
+ * (uint32)i * 923766u, the seeds of pixels (i, 0).  PT_E_STATE before pt_upload_scene; PT_E_ARG for a null rays or
+ * rgba with n > 0, n < 0, frame_first < 1, n_frames < 1, frame_first + n_frames overflowing int, or accumulate_first
+ * not 0 or 1; n = 0 is PT_OK without a launch.  A row-split context answers like any other. */
+int pt_trace(pt_ctx* ctx, const pt_ray* rays, const unsigned* seeds, long long n, int frame_first, int n_frames,
+             int accumulate_first, float* rgba);
+/* The same on device arrays (d_rays and d_rgba 16-byte aligned, d_seeds 4-byte aligned or NULL; else PT_E_ARG),
+ * enqueued on the context's stream (pt_stream) and not synchronised.  It allocates nothing. */
+int pt_trace_device(pt_ctx* ctx, const void* d_rays, const void* d_seeds, long long n, int frame_first, int n_frames,
+                    int accumulate_first, void* d_rgba);
+/* The pixel part of the reference's seed, y * 831266u + x * 923766u, of n pixels xy = {x0, y0, ...}.  Pure host code. */
+int pt_pixel_seeds(const int* xy, long long n, unsigned* seeds_out);
+/* The trace on the host, of a scene in pt_upload_scene's arrays: packs it as pt_upload_scene does and runs the
+ * device kernel's own per-ray code.  No device is touched.  ctx_flags, max_bounce, display_mode: what a context
+ * would hold.  Returns the packer's error for a rejected scene. */
+int pt_trace_host(const float* tris, int n_tris, const float* bvh, int n_nodes, const float* mats, int n_mats,
+                  const float* spheres, int n_spheres, int ctx_flags, int max_bounce, int display_mode,
+                  const pt_ray* rays, const unsigned* seeds, long long n, int frame_first, int n_frames,
+                  int accumulate_first, float* rgba);
+
 #ifdef __cplusplus
 }
 #endif

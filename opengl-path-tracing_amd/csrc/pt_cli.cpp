@@ -69,6 +69,10 @@ static void usage() {
                  "                  p and the material's albedo (t and albedo null for a miss)\n"
                  "  --rays F --hits G [--any-hit]  cast the raw 32-byte rays of F (pt_api.h: pt_ray, pt_intersect)\n"
                  "                  and write the raw 48-byte hit records to G\n"
+                 "  --rays F --radiance G [--seeds S] [--spp N]  trace the rays of F (pt_api.h: pt_trace), frames 1..N\n"
+                 "                  (default 1), and write one raw RGBA32F record per ray to G; S: one raw uint32 seed\n"
+                 "                  per ray (default: those of pixels (i, 0)); with --spp, --pick lines gain\n"
+                 "                  \"radiance\", the traced colour of the pixel's ray over frames 1..N\n"
                  "                  queries run on context 0 after the render; without --spp, --noise-target and\n"
                  "                  --events they run alone: nothing is rendered and no image is written\n");
 }
@@ -206,7 +210,7 @@ int main(int argc, char** argv) {
     std::string denoise_pfm, denoise_ppm;
     double denoise_ms = 0.0;
     std::vector<int> picks;               // x, y pairs
-    std::string rays_path, hits_path;
+    std::string rays_path, hits_path, radiance_path, seeds_path;
     bool any_hit = false, spp_given = false;
     for (int i = 3; i < argc; i++) {
         std::string a = argv[i];
@@ -247,6 +251,8 @@ int main(int argc, char** argv) {
         else if (a == "--rays") rays_path = next();
         else if (a == "--hits") hits_path = next();
         else if (a == "--any-hit") any_hit = true;
+        else if (a == "--radiance") radiance_path = next();
+        else if (a == "--seeds") seeds_path = next();
         else { usage(); return 2; }
     }
     if (ranks == 0) ranks = gpus;
@@ -263,10 +269,12 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--denoise-pfm / --denoise-ppm need --denoise\n");
         return 2;
     }
-    if (rays_path.empty() != hits_path.empty() || (any_hit && rays_path.empty())) {
-        std::fprintf(stderr, "--rays and --hits go together, --any-hit with them\n");
+    if (rays_path.empty() != (hits_path.empty() && radiance_path.empty()) || (any_hit && hits_path.empty()) ||
+        (!seeds_path.empty() && radiance_path.empty())) {
+        std::fprintf(stderr, "--rays goes with --hits or --radiance, --any-hit with --hits, --seeds with --radiance\n");
         return 2;
     }
+    const int trace_frames = spp_given ? spp : 1;   // of --radiance and of a --pick line's colour
     const bool queries = !picks.empty() || !rays_path.empty();
     const bool query_only = queries && !spp_given && !until && !events && !denoise && resume.empty() && checkpoint.empty();
     if (adaptive && !until) {
@@ -359,6 +367,14 @@ int main(int argc, char** argv) {
         if (!picks.empty()) {
             std::vector<pt_hit> h(picks.size() / 2);
             CHECK(pt_pick(ctx[0], picks.data(), (long long)h.size(), h.data()), ctx[0]);
+            std::vector<float> colour(4 * h.size());
+            if (spp_given) {                  // the radiance behind the pixel: its ray and its seed, frames 1..spp
+                std::vector<pt_ray> pr(h.size());
+                std::vector<unsigned> ps(h.size());
+                if (pt_pixel_rays(W, H, cam, picks.data(), (long long)h.size(), pr.data()) ||
+                    pt_pixel_seeds(picks.data(), (long long)h.size(), ps.data())) return 1;
+                CHECK(pt_trace(ctx[0], pr.data(), ps.data(), (long long)h.size(), 1, trace_frames, 0, colour.data()), ctx[0]);
+            }
             for (size_t i = 0; i < h.size(); i++) {
                 std::printf("{\"pick\": [%d, %d], \"kind\": %d, \"prim\": %d, \"mat\": %d, ", picks[2 * i], picks[2 * i + 1],
                             h[i].kind, h[i].prim, h[i].mat);
@@ -366,9 +382,11 @@ int main(int argc, char** argv) {
                 else std::printf("\"t\": %.9g, ", h[i].t);
                 std::printf("\"n\": [%.9g, %.9g, %.9g], \"p\": [%.9g, %.9g, %.9g], ", h[i].n[0], h[i].n[1], h[i].n[2],
                             h[i].p[0], h[i].p[1], h[i].p[2]);
-                if (h[i].kind == PT_HIT_NONE) std::printf("\"albedo\": null}\n");
-                else std::printf("\"albedo\": [%.9g, %.9g, %.9g]}\n", mats[16 * (size_t)h[i].mat], mats[16 * (size_t)h[i].mat + 1],
+                if (h[i].kind == PT_HIT_NONE) std::printf("\"albedo\": null");
+                else std::printf("\"albedo\": [%.9g, %.9g, %.9g]", mats[16 * (size_t)h[i].mat], mats[16 * (size_t)h[i].mat + 1],
                                  mats[16 * (size_t)h[i].mat + 2]);
+                if (spp_given) std::printf(", \"radiance\": [%.9g, %.9g, %.9g]", colour[4 * i], colour[4 * i + 1], colour[4 * i + 2]);
+                std::printf("}\n");
             }
         }
         if (!rays_path.empty()) {
@@ -378,14 +396,35 @@ int main(int argc, char** argv) {
             pt_ray r;
             while (std::fread(&r, sizeof(r), 1, f) == 1) rays.push_back(r);
             std::fclose(f);
-            std::vector<pt_hit> h(rays.size());
-            CHECK(pt_intersect(ctx[0], rays.data(), (long long)rays.size(), h.data(), any_hit ? PT_QUERY_ANY_HIT : 0), ctx[0]);
-            f = std::fopen(hits_path.c_str(), "wb");
-            if (!f || std::fwrite(h.data(), sizeof(pt_hit), h.size(), f) != h.size()) {
-                std::fprintf(stderr, "cannot write %s\n", hits_path.c_str());
-                return 1;
+            if (!hits_path.empty()) {
+                std::vector<pt_hit> h(rays.size());
+                CHECK(pt_intersect(ctx[0], rays.data(), (long long)rays.size(), h.data(), any_hit ? PT_QUERY_ANY_HIT : 0), ctx[0]);
+                f = std::fopen(hits_path.c_str(), "wb");
+                if (!f || std::fwrite(h.data(), sizeof(pt_hit), h.size(), f) != h.size()) {
+                    std::fprintf(stderr, "cannot write %s\n", hits_path.c_str());
+                    return 1;
+                }
+                std::fclose(f);
             }
-            std::fclose(f);
+            if (!radiance_path.empty()) {
+                std::vector<unsigned> seeds;
+                if (!seeds_path.empty()) {
+                    seeds.resize(rays.size());
+                    f = std::fopen(seeds_path.c_str(), "rb");
+                    const bool ok = f && std::fread(seeds.data(), sizeof(unsigned), seeds.size(), f) == seeds.size();
+                    if (f) std::fclose(f);
+                    if (!ok) { std::fprintf(stderr, "%s: cannot read one seed per ray\n", seeds_path.c_str()); return 1; }
+                }
+                std::vector<float> rgba(4 * rays.size());
+                CHECK(pt_trace(ctx[0], rays.data(), seeds.empty() ? nullptr : seeds.data(), (long long)rays.size(), 1,
+                               trace_frames, 0, rgba.data()), ctx[0]);
+                f = std::fopen(radiance_path.c_str(), "wb");
+                if (!f || std::fwrite(rgba.data(), 16, rays.size(), f) != rays.size()) {
+                    std::fprintf(stderr, "cannot write %s\n", radiance_path.c_str());
+                    return 1;
+                }
+                std::fclose(f);
+            }
         }
         return 0;
     };

@@ -28,6 +28,7 @@
 #include "pt_noise.h"
 #include "pt_pool.h"
 #include "pt_query_launch.h"
+#include "pt_trace_launch.h"
 #include "pt_render_kernels.h"
 #include "pt_scene_pack.h"
 #include "pt_wide.h"
@@ -895,6 +896,17 @@ int pt__query_view(const pt_ctx* c, ptq::CtxView* out) {
     return PT_OK;
 }
 int pt__query_fail(pt_ctx* c, int code, const char* msg) { return fail(c, code, msg ? msg : ""); }
+
+// The traced rays' view (pt_trace_kernels.hip; internal, not part of the public ABI): the query's, with the materials
+// and the two settings a path reads beside it.  Changes nothing in the context either.
+int pt__trace_view(const pt_ctx* c, ptt::CtxView* out) {
+    if (!c || !out) return PT_E_ARG;
+    const int rc = pt__query_view(c, &out->q);
+    if (rc) return rc;
+    out->mats = c->d_scene[ptp::kMats];
+    out->max_bounce = c->cfg.max_bounce, out->mode = c->cfg.display_mode;
+    return PT_OK;
+}
 
 }  // extern "C"
 

@@ -191,6 +191,10 @@ def lib():
             "pt_pixel_rays": (ip, [ip, ip, _F, vp, C.c_longlong, vp]),
             "pt_pick": (ip, [vp, vp, C.c_longlong, vp]),
             "pt_intersect_host": (ip, [_F, ip, _F, ip, _F, ip, _F, ip, ip, vp, C.c_longlong, vp, ip]),
+            "pt_trace": (ip, [vp, vp, vp, C.c_longlong, ip, ip, ip, vp]),
+            "pt_trace_device": (ip, [vp, vp, vp, C.c_longlong, ip, ip, ip, vp]),
+            "pt_pixel_seeds": (ip, [vp, C.c_longlong, vp]),
+            "pt_trace_host": (ip, [_F, ip, _F, ip, _F, ip, _F, ip, ip, ip, ip, vp, vp, C.c_longlong, ip, ip, ip, vp]),
             "pt_group_create": (ip, [C.POINTER(vp), ip, C.POINTER(vp)]),
             "pt_group_destroy": (None, [vp]),
             "pt_group_last_error": (C.c_char_p, [vp]),
@@ -657,6 +661,25 @@ class PathTracer:
         self._check(lib().pt_pick(self.h, xy.ctypes.data, len(xy), hits.ctypes.data))
         return hits
 
+    def trace(self, rays, seeds=None, frame_first=1, n_frames=1, prior=None):
+        """pt_trace: the radiance along each ray (RAY_DTYPE or (n, 8) float32), frames frame_first ..
+        frame_first + n_frames - 1 folded in frame order -> (n, 4) float32, synchronous.  seeds: (n,) uint32 (None:
+        those of pixels (i, 0)).  prior: (n, 4) float32 the first frame averages over (None: it overwrites)."""
+        rays = _rays_in(rays)
+        seeds = _seeds_in(seeds, len(rays))
+        out = _prior_in(prior, len(rays))
+        self._check(lib().pt_trace(self.h, rays.ctypes.data, None if seeds is None else seeds.ctypes.data, len(rays),
+                                   int(frame_first), int(n_frames), int(prior is not None), out.ctypes.data))
+        return out
+
+    def trace_device(self, rays_ptr, seeds_ptr, n, rgba_ptr, frame_first=1, n_frames=1, accumulate_first=0):
+        """pt_trace_device: n rays at device pointer rays_ptr (32 B each), seeds at seeds_ptr (4 B each, or None) ->
+        running means at rgba_ptr (16 B each, in/out); enqueued on the context's stream (stream()), not
+        synchronised."""
+        self._check(lib().pt_trace_device(self.h, C.c_void_p(int(rays_ptr)),
+                                          C.c_void_p(int(seeds_ptr)) if seeds_ptr else None, int(n), int(frame_first),
+                                          int(n_frames), int(accumulate_first), C.c_void_p(int(rgba_ptr))))
+
     def diag(self):
         """Lane utilisation per kernel phase from the last counting render."""
         v = np.zeros(16, np.uint64)
@@ -891,6 +914,52 @@ def intersect_host(sb, rays, any_hit=False, flags=0):
     if rc:
         raise PTError(rc, "pt_intersect_host: rejected scene or bad arguments")
     return hits
+
+
+# ----------------------------------------------------------------------------- traced rays
+def _seeds_in(seeds, n):
+    if seeds is None:
+        return None
+    s = np.ascontiguousarray(seeds, np.uint32).reshape(-1)
+    if len(s) != n:
+        raise ValueError("one seed per ray")
+    return s
+
+
+def _prior_in(prior, n):
+    """The in/out array of a trace: a copy of the prior, or NaNs a trace that overwrites never reads."""
+    if prior is None:
+        return np.full((n, 4), np.nan, np.float32)
+    out = np.array(prior, np.float32).reshape(-1, 4)
+    if len(out) != n:
+        raise ValueError("one prior RGBA per ray")
+    return out
+
+
+def pixel_seeds(xy):
+    """pt_pixel_seeds: the pixel part of the reference's seed, y * 831266 + x * 923766 (mod 2^32), of (n, 2) pixels."""
+    xy = _xy_in(xy)
+    seeds = np.zeros(len(xy), np.uint32)
+    rc = lib().pt_pixel_seeds(xy.ctypes.data, len(xy), seeds.ctypes.data)
+    if rc:
+        raise PTError(rc, "pt_pixel_seeds: bad arrays")
+    return seeds
+
+
+def trace_host(sb, rays, seeds=None, frame_first=1, n_frames=1, prior=None, flags=0, max_bounce=5, mode=1):
+    """pt_trace_host: traced rays on the host (no device) -- the per-ray code is the device kernel's own, run on the
+    buffers ptp::pack_scene makes of the scene `sb`.  flags, max_bounce, mode: what a context would hold."""
+    rays = _rays_in(rays)
+    seeds = _seeds_in(seeds, len(rays))
+    out = _prior_in(prior, len(rays))
+    t, n, m, s = _f32(sb["tris"], 16), _f32(sb["nodes"], 12), _f32(sb["mats"], 16), _f32(sb["spheres"], 8)
+    z = lambda a, c: a.reshape(-1) if a.size else np.zeros(c, np.float32)
+    rc = lib().pt_trace_host(z(t, 16), len(t), z(n, 12), len(n), z(m, 16), len(m), z(s, 8), len(s), int(flags),
+                             int(max_bounce), int(mode), rays.ctypes.data, None if seeds is None else seeds.ctypes.data,
+                             len(rays), int(frame_first), int(n_frames), int(prior is not None), out.ctypes.data)
+    if rc:
+        raise PTError(rc, "pt_trace_host: rejected scene or bad arguments")
+    return out
 
 
 def noise_host(moments, frames, target, in_footprint=None):
