@@ -430,9 +430,10 @@ int pt_intersect_host(const float* tris, int n_tris, const float* bvh, int n_nod
                       const float* spheres, int n_spheres, int ctx_flags, const pt_ray* rays, long long n,
                       pt_hit* hits, int query_flags);
 
-/* Traced rays: the light that arrives along a caller's ray -- cameras other than the built-in
- * pinhole (panoramas, orthographic views, stereo pairs, a thin lens), light probes and lightmap baking, the radiance
- * behind a picked pixel, an integrator the client drives itself.
+/* Traced rays: the light that arrives along a caller's ray -- cameras the caller builds itself
+ * (fisheye, stereo pairs), light probes and lightmap baking, the radiance behind a picked pixel, an integrator the
+ * client drives itself.  A thin lens, orthographic views and anti-aliased panoramas are camera models (pt_trace_camera
+ * below): a traced ray is the same in every frame of a call.
  *
  * For ray i and frame f the random state is seeds[i] + (uint32)f * 719393u, wrapping, and rgb is the reference's
  * Trace (computeShader.c:434-501) from o, d with that state: incoming light 0, ray colour 1, and for every segment up
@@ -473,6 +474,80 @@ int pt_trace_host(const float* tris, int n_tris, const float* bvh, int n_nodes, 
                   const float* spheres, int n_spheres, int ctx_flags, int max_bounce, int display_mode,
                   const pt_ray* rays, const unsigned* seeds, long long n, int frame_first, int n_frames,
                   int accumulate_first, float* rgba);
+
+/* Camera models: depth of field, orthographic views and anti-aliased panoramas.  The camera is a
+ * function of (pixel, frame, random state) evaluated inside the trace kernel: a lane makes its own ray at the start of
+ * every path, so nothing is uploaded per sample and every frame of a call has its own jitter and lens sample.
+ *
+ * For pixel (x, y) of frame f the state starts as the reference's seed, y * 831266u + x * 923766u + f * 719393u, and
+ * the camera takes its draws from it before Trace does, in this order: unless PT_CAM_NO_AA is set, ax then ay (the
+ * reference's jitter; otherwise both are 0 and nothing is drawn); then the model's own, u1 then u2 for the thin lens
+ * and none for the others.  u = (x + ax) / width - 0.5 and v = (y + ay) / height - 0.5.  With {pos, fwd, right, up}
+ * as pt_set_camera derives them from cam (up scaled by height / width), upU = normalize(cross(right, fwd)) and
+ * pi = 3.1415926f:
+ *   PT_CAM_PINHOLE    o = pos, d = normalize(fwd + right u + up v): the built-in camera.
+ *   PT_CAM_THIN_LENS  D = fwd + right u + up v, P = pos + D focus (the plane at distance `focus` along fwd is sharp),
+ *                     r = aperture sqrt(u1), phi = 2 pi u2, o = pos + right r cos phi + upU r sin phi,
+ *                     d = normalize(P - o).
+ *   PT_CAM_ORTHO      o = pos + right (u ortho_width) + up (v ortho_width), d = fwd.
+ *   PT_CAM_EQUIRECT   theta = 2 pi (u + 0.5), alpha = pi (v + 0.5), F = normalize(fwd.x, fwd.y, 0),
+ *                     d = normalize((F (-cos theta) + right (-sin theta)) sin alpha + (0, 0, -cos alpha)), o = pos:
+ *                     the centre column looks along F, columns to its right look to the right, row 0 looks down.
+ * d is normalised and t_max = +inf.  The arithmetic is pinned (csrc/pt_camera.h) and the same on host and device.
+ * Nothing is special-cased: a fwd parallel to z makes NaN rays, as it does in the reference.
+ *
+ * Frame f of pixel i = y * width + x is the reference's Trace from that ray and the state the camera left; the
+ * frames of a pixel are folded into rgba[i] as pt_trace folds a ray's (pt_render's rule).  One ray per pixel: more
+ * samples are more frames.
+ *
+ * Consequence: pt_trace_camera(PT_CAM_PINHOLE, flags 0, .., F, N, A, rgba) writes the pixels of pt_render(F, N, A) on
+ * a default (flags 0, one-ray-per-pixel) context of that size and camera, bit for bit; with PT_CAM_NO_AA those of a
+ * PT_FLAG_NO_AA context.
+ *
+ * The context's scene, max_bounce, display mode, PT_FLAG_NO_SKY, PT_FLAG_NO_SPHERES, PT_FLAG_NO_TRIANGLES and
+ * PT_FLAG_MOLLER_TRUMBORE apply as in pt_trace; its PT_FLAG_NO_AA, PT_FLAG_REF_DISPATCH, size, camera and row split
+ * mean nothing here: the camera's size and flag are its own.  Like a query and a trace, these calls are invisible to
+ * rendering. */
+#define PT_CAM_PINHOLE 0
+#define PT_CAM_THIN_LENS 1
+#define PT_CAM_ORTHO 2
+#define PT_CAM_EQUIRECT 3
+#define PT_CAM_NO_AA 1
+typedef struct {
+    int model;               /* PT_CAM_* */
+    int width, height;       /* 1..65536, as pt_create allows */
+    int flags;               /* PT_CAM_NO_AA */
+    float cam[12];           /* as pt_set_camera */
+    float aperture;          /* lens radius, thin lens; >= 0 */
+    float focus;             /* distance of the plane in focus along fwd, thin lens; > 0 */
+    float ortho_width;       /* world width of the view, ortho; > 0 */
+    float pad;               /* 0 */
+} pt_camera;                 /* 80 B */
+/* Frames frame_first .. frame_first + n_frames - 1 of every pixel; rgba: a host array of width * height * 4 floats,
+ * in and out, in the pixel order of pt_read_rgba32f on an unsplit context (row 0 = bottom).  Synchronous.
+ * PT_E_STATE before pt_upload_scene; PT_E_ARG for the frame and accumulate_first errors of pt_trace, a null rgba or
+ * camera, an unknown model or camera flag, a size out of range, and a NaN, negative or (focus, ortho_width) zero
+ * aperture, focus or ortho_width for the model that reads it.  Fields a model does not read are ignored. */
+int pt_trace_camera(pt_ctx* ctx, const pt_camera* camera, int frame_first, int n_frames, int accumulate_first,
+                    float* rgba);
+/* The same on a device array (16-byte aligned, else PT_E_ARG), enqueued on the context's stream (pt_stream) and not
+ * synchronised.  It allocates nothing. */
+int pt_trace_camera_device(pt_ctx* ctx, const pt_camera* camera, int frame_first, int n_frames, int accumulate_first,
+                           void* d_rgba);
+/* The same on the host, of a scene in pt_upload_scene's arrays: packs it as pt_upload_scene does and runs the device
+ * kernel's own per-pixel code.  No device is touched.  Returns the packer's error for a rejected scene. */
+int pt_trace_camera_host(const float* tris, int n_tris, const float* bvh, int n_nodes, const float* mats, int n_mats,
+                         const float* spheres, int n_spheres, int ctx_flags, int max_bounce, int display_mode,
+                         const pt_camera* camera, int frame_first, int n_frames, int accumulate_first, float* rgba);
+/* The ray of each of the n pixels xy = {x0, y0, ...} in frame `frame` (>= 1), and in states_out (may be NULL) the
+ * random state after the camera's draws: pt_trace of rays_out[i] with seed states_out[i] - frame * 719393u is that
+ * pixel's frame.  Pure host code.  PT_E_ARG also for a pixel outside the image (nothing is written then). */
+int pt_camera_rays_host(const pt_camera* camera, const int* xy, long long n, int frame, pt_ray* rays_out,
+                        unsigned* states_out);
+/* The same for every pixel of the image, in pixel order, into device arrays (d_rays 16-byte aligned, width * height
+ * rays; d_states 4-byte aligned or NULL), enqueued on the context's stream and not synchronised: the input of a
+ * pt_intersect_device (a depth buffer through the lens) or a pt_trace_device.  Needs no uploaded scene. */
+int pt_camera_rays_device(pt_ctx* ctx, const pt_camera* camera, int frame, void* d_rays, void* d_states);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,7 @@
 #include "../../include/pt_viewer.h"
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -74,7 +75,16 @@ static void usage() {
                  "                  per ray (default: those of pixels (i, 0)); with --spp, --pick lines gain\n"
                  "                  \"radiance\", the traced colour of the pixel's ray over frames 1..N\n"
                  "                  queries run on context 0 after the render; without --spp, --noise-target and\n"
-                 "                  --events they run alone: nothing is rendered and no image is written\n");
+                 "                  --events they run alone: nothing is rendered and no image is written\n"
+                 "  --camera-model pinhole|thinlens|ortho|equirect  render frames 1..--spp through a camera model\n"
+                 "                  (pt_api.h: pt_camera, pt_trace_camera), --chunk frames per call, at --width x\n"
+                 "                  --height from --camera; the image is stored in the context, so --pfm, --ppm, --json\n"
+                 "                  and --pick work as ever.  --aperture R (lens radius) and --focus D (distance of the\n"
+                 "                  sharp plane along the view direction) or --focus-at X,Y (D = dot(p - pos, fwd) of\n"
+                 "                  what --pick finds under that pixel, in binary32) for thinlens; --ortho-width W (world\n"
+                 "                  width of the view) for ortho; --no-aa: no jitter.  One context only: not with --gpus\n"
+                 "                  above 1, --ranks, --adaptive, --noise-target, --denoise*, --events, --checkpoint,\n"
+                 "                  --resume, --rays, --hits, --radiance or --seeds\n");
 }
 
 // Checkpoint of a progressive render (SURVEY.md §5 checkpoint / resume): the running mean
@@ -212,6 +222,10 @@ int main(int argc, char** argv) {
     std::vector<int> picks;               // x, y pairs
     std::string rays_path, hits_path, radiance_path, seeds_path;
     bool any_hit = false, spp_given = false;
+    int cam_model = -1;                   // >= 0: render through pt_trace_camera
+    pt_camera pcam = {PT_CAM_PINHOLE, 0, 0, 0, {0}, 0.0f, 1.0f, 1.0f, 0.0f};
+    bool focus_at = false, lens_given = false, ranks_given = false;
+    int focus_xy[2] = {0, 0};
     for (int i = 3; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&](void) -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
@@ -222,7 +236,7 @@ int main(int argc, char** argv) {
         else if (a == "--bounces") bounces = std::atoi(next());
         else if (a == "--mode") mode = std::atoi(next());
         else if (a == "--gpus") gpus = std::atoi(next());
-        else if (a == "--ranks") ranks = std::atoi(next());
+        else if (a == "--ranks") { ranks = std::atoi(next()); ranks_given = true; }
         else if (a == "--pfm") pfm = next();
         else if (a == "--ppm") ppm = next();
         else if (a == "--camera") { for (int k = 0; k < 6; k++) cam[k < 3 ? k : k + 1] = (float)std::atof(next()); }
@@ -253,9 +267,36 @@ int main(int argc, char** argv) {
         else if (a == "--any-hit") any_hit = true;
         else if (a == "--radiance") radiance_path = next();
         else if (a == "--seeds") seeds_path = next();
+        else if (a == "--camera-model") {
+            const std::string m = next();
+            cam_model = m == "pinhole" ? PT_CAM_PINHOLE : m == "thinlens" ? PT_CAM_THIN_LENS : m == "ortho" ? PT_CAM_ORTHO
+                      : m == "equirect" ? PT_CAM_EQUIRECT : -1;
+            if (cam_model < 0) { std::fprintf(stderr, "--camera-model is one of pinhole, thinlens, ortho, equirect\n"); return 2; }
+        }
+        else if (a == "--aperture") { pcam.aperture = (float)std::atof(next()); lens_given = true; }
+        else if (a == "--focus") { pcam.focus = (float)std::atof(next()); lens_given = true; }
+        else if (a == "--focus-at") {
+            if (std::sscanf(next(), "%d,%d", &focus_xy[0], &focus_xy[1]) != 2) { usage(); return 2; }
+            focus_at = lens_given = true;
+        }
+        else if (a == "--ortho-width") { pcam.ortho_width = (float)std::atof(next()); lens_given = true; }
+        else if (a == "--no-aa") { pcam.flags |= PT_CAM_NO_AA; lens_given = true; }
         else { usage(); return 2; }
     }
     if (ranks == 0) ranks = gpus;
+    if (cam_model < 0 && lens_given) {
+        std::fprintf(stderr, "--aperture, --focus, --focus-at, --ortho-width and --no-aa need --camera-model\n");
+        return 2;
+    }
+    if (cam_model >= 0) {
+        // one context, frames 1..spp, nothing that owns the render loop or the traced-ray options
+        const char* clash = gpus > 1 ? "--gpus above 1" : ranks_given ? "--ranks" : adaptive ? "--adaptive"
+                          : until ? "--noise-target" : (denoise || !denoise_pfm.empty() || !denoise_ppm.empty()) ? "--denoise"
+                          : events ? "--events" : !checkpoint.empty() ? "--checkpoint" : !resume.empty() ? "--resume"
+                          : !rays_path.empty() ? "--rays" : !hits_path.empty() ? "--hits" : !radiance_path.empty() ? "--radiance"
+                          : !seeds_path.empty() ? "--seeds" : nullptr;
+        if (clash) { std::fprintf(stderr, "--camera-model excludes %s\n", clash); return 2; }
+    }
     if (spp < 1 || chunk < 1 || gpus < 1 || ranks < 1) { usage(); return 2; }
     if (events && (!resume.empty() || !checkpoint.empty())) {
         std::fprintf(stderr, "--events excludes --resume / --checkpoint\n");
@@ -276,7 +317,8 @@ int main(int argc, char** argv) {
     }
     const int trace_frames = spp_given ? spp : 1;   // of --radiance and of a --pick line's colour
     const bool queries = !picks.empty() || !rays_path.empty();
-    const bool query_only = queries && !spp_given && !until && !events && !denoise && resume.empty() && checkpoint.empty();
+    const bool query_only = queries && !spp_given && !until && !events && !denoise && resume.empty() && checkpoint.empty() &&
+                            cam_model < 0;
     if (adaptive && !until) {
         std::fprintf(stderr, "--adaptive needs --noise-target\n");
         return 2;
@@ -491,6 +533,29 @@ int main(int argc, char** argv) {
             CHECK(pt_render_until(ctx[0], 1, 0, batch, max_spp, noise_target, &done, &noise), ctx[0]);
         }
         spp = done;
+    } else if (cam_model >= 0) {
+        // frames 1..spp through the camera model, then the image into the context for the reads below
+        pcam.model = cam_model, pcam.width = W, pcam.height = H;
+        std::memcpy(pcam.cam, cam, sizeof(cam));
+        if (focus_at) {
+            pt_hit h;
+            CHECK(pt_pick(ctx[0], focus_xy, 1, &h), ctx[0]);
+            if (h.kind == PT_HIT_NONE) {
+                std::fprintf(stderr, "--focus-at %d,%d: nothing under that pixel to focus on\n", focus_xy[0], focus_xy[1]);
+                return 1;
+            }
+            // dot(p - pos, fwd) in binary32: fwd = dir * (1 / sqrt(dot(dir, dir))), dot = (x + y) + z
+            const float q = (cam[4] * cam[4] + cam[5] * cam[5]) + cam[6] * cam[6], r = 1.0f / std::sqrt(q);
+            const float fx = cam[4] * r, fy = cam[5] * r, fz = cam[6] * r;
+            pcam.focus = ((h.p[0] - cam[0]) * fx + (h.p[1] - cam[1]) * fy) + (h.p[2] - cam[2]) * fz;
+            std::printf("focus at pixel (%d, %d): %.9g\n", focus_xy[0], focus_xy[1], pcam.focus);
+        }
+        std::vector<float> cimg(4 * (size_t)W * H, 0.0f);
+        for (int k = 0; k < spp; k += chunk) {
+            const int n = std::min(chunk, spp - k), f0 = 1 + k;
+            CHECK(pt_trace_camera(ctx[0], &pcam, f0, n, f0 == 1 ? 0 : 1, cimg.data()), ctx[0]);
+        }
+        CHECK(pt_write_rgba32f(ctx[0], cimg.data(), cimg.size() * 4), ctx[0]);
     } else {
         for (int k = 0; k < spp; k += chunk) {
             const int n = std::min(chunk, spp - k), f0 = first + k;

@@ -96,6 +96,7 @@ __global__ __launch_bounds__(kThreads) void k_trace(TraceArgs a) {
         }
         return;
     }
+    // TWIN: k_trace_camera (pt_camera_kernels.hip) restates this refill loop with the ray made by the lane, not loaded.
     // the wave's share: cursor position c is ray (c / 64) * 64 * Wn + 64 * w + c % 64
     const long long w = (long long)blockIdx.x * kWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const long long Wn = (long long)gridDim.x * kWaves;

@@ -88,6 +88,34 @@ class DenoiseInfo(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("guided", "guides_rendered", "iterations", "frames")]
 
 
+PT_CAM_PINHOLE, PT_CAM_THIN_LENS, PT_CAM_ORTHO, PT_CAM_EQUIRECT = 0, 1, 2, 3
+PT_CAM_NO_AA = 1
+CAMERA_MODELS = {"pinhole": PT_CAM_PINHOLE, "thinlens": PT_CAM_THIN_LENS, "ortho": PT_CAM_ORTHO,
+                 "equirect": PT_CAM_EQUIRECT}
+
+
+class Camera(C.Structure):
+    """pt_camera (include/pt_api.h): Camera("thinlens", W, H, cam, aperture=0.05, focus=6.0),
+    Camera("ortho", W, H, cam, ortho_width=4.0), Camera("equirect", W, H, cam, aa=False), ...  model: a name of
+    CAMERA_MODELS or a PT_CAM_* value; cam: the 12 floats of pt_set_camera (None: the reference's default)."""
+    _fields_ = [("model", C.c_int), ("width", C.c_int), ("height", C.c_int), ("flags", C.c_int),
+                ("cam", C.c_float * 12), ("aperture", C.c_float), ("focus", C.c_float), ("ortho_width", C.c_float),
+                ("pad", C.c_float)]
+
+    def __init__(self, model="pinhole", width=1, height=1, cam=None, aperture=0.0, focus=1.0, ortho_width=1.0,
+                 aa=True, flags=None):
+        super().__init__()
+        self.model = CAMERA_MODELS[model] if isinstance(model, str) else int(model)
+        self.width, self.height = int(width), int(height)
+        self.flags = int(flags) if flags is not None else (0 if aa else PT_CAM_NO_AA)
+        self.cam[:] = [float(v) for v in np.asarray(DEFAULT_CAMERA if cam is None else cam, np.float32).reshape(12)]
+        self.aperture, self.focus, self.ortho_width = float(aperture), float(focus), float(ortho_width)
+
+    @property
+    def pixels(self):
+        return self.width * self.height
+
+
 def denoise_params(**params):
     """pt_denoise_defaults, with the given fields replaced."""
     p = DenoiseParams()
@@ -195,6 +223,11 @@ def lib():
             "pt_trace_device": (ip, [vp, vp, vp, C.c_longlong, ip, ip, ip, vp]),
             "pt_pixel_seeds": (ip, [vp, C.c_longlong, vp]),
             "pt_trace_host": (ip, [_F, ip, _F, ip, _F, ip, _F, ip, ip, ip, ip, vp, vp, C.c_longlong, ip, ip, ip, vp]),
+            "pt_trace_camera": (ip, [vp, C.POINTER(Camera), ip, ip, ip, vp]),
+            "pt_trace_camera_device": (ip, [vp, C.POINTER(Camera), ip, ip, ip, vp]),
+            "pt_trace_camera_host": (ip, [_F, ip, _F, ip, _F, ip, _F, ip, ip, ip, ip, C.POINTER(Camera), ip, ip, ip, vp]),
+            "pt_camera_rays_host": (ip, [C.POINTER(Camera), vp, C.c_longlong, ip, vp, vp]),
+            "pt_camera_rays_device": (ip, [vp, C.POINTER(Camera), ip, vp, vp]),
             "pt_group_create": (ip, [C.POINTER(vp), ip, C.POINTER(vp)]),
             "pt_group_destroy": (None, [vp]),
             "pt_group_last_error": (C.c_char_p, [vp]),
@@ -680,6 +713,28 @@ class PathTracer:
                                           C.c_void_p(int(seeds_ptr)) if seeds_ptr else None, int(n), int(frame_first),
                                           int(n_frames), int(accumulate_first), C.c_void_p(int(rgba_ptr))))
 
+    def trace_camera(self, camera, frame_first=1, n_frames=1, prior=None):
+        """pt_trace_camera: frames frame_first .. frame_first + n_frames - 1 of every pixel of the Camera, folded in
+        frame order -> (height, width, 4) float32 (row 0 = bottom), synchronous.  prior: the image the first frame
+        averages over (None: it overwrites)."""
+        out = _prior_in(prior, camera.pixels)
+        self._check(lib().pt_trace_camera(self.h, C.byref(camera), int(frame_first), int(n_frames),
+                                          int(prior is not None), out.ctypes.data))
+        return out.reshape(camera.height, camera.width, 4)
+
+    def trace_camera_device(self, camera, rgba_ptr, frame_first=1, n_frames=1, accumulate_first=0):
+        """pt_trace_camera_device: the same into the running means at device pointer rgba_ptr (16 B per pixel,
+        in/out); enqueued on the context's stream (stream()), not synchronised."""
+        self._check(lib().pt_trace_camera_device(self.h, C.byref(camera), int(frame_first), int(n_frames),
+                                                 int(accumulate_first), C.c_void_p(int(rgba_ptr))))
+
+    def camera_rays_device(self, camera, frame, rays_ptr, states_ptr=None):
+        """pt_camera_rays_device: the Camera's ray of every pixel in frame `frame` at device pointer rays_ptr (32 B
+        each, pixel order) and, where given, the random state after the camera's draws at states_ptr (4 B each);
+        enqueued on the context's stream, not synchronised."""
+        self._check(lib().pt_camera_rays_device(self.h, C.byref(camera), int(frame), C.c_void_p(int(rays_ptr)),
+                                                C.c_void_p(int(states_ptr)) if states_ptr else None))
+
     def diag(self):
         """Lane utilisation per kernel phase from the last counting render."""
         v = np.zeros(16, np.uint64)
@@ -960,6 +1015,33 @@ def trace_host(sb, rays, seeds=None, frame_first=1, n_frames=1, prior=None, flag
     if rc:
         raise PTError(rc, "pt_trace_host: rejected scene or bad arguments")
     return out
+
+
+# ----------------------------------------------------------------------------- camera models
+def camera_rays_host(camera, xy, frame=1):
+    """pt_camera_rays_host: the Camera's rays of the (n, 2) pixels xy in frame `frame`, on the host -> (RAY_DTYPE
+    rays, (n,) uint32 random states after the camera's draws)."""
+    xy = _xy_in(xy)
+    rays, states = np.zeros(len(xy), RAY_DTYPE), np.zeros(len(xy), np.uint32)
+    rc = lib().pt_camera_rays_host(C.byref(camera), xy.ctypes.data, len(xy), int(frame), rays.ctypes.data,
+                                   states.ctypes.data)
+    if rc:
+        raise PTError(rc, "pt_camera_rays_host: bad camera, frame or arrays")
+    return rays, states
+
+
+def trace_camera_host(sb, camera, frame_first=1, n_frames=1, prior=None, flags=0, max_bounce=5, mode=1):
+    """pt_trace_camera_host: pt_trace_camera on the host (no device) -- the per-pixel code is the device kernel's own,
+    run on the buffers ptp::pack_scene makes of the scene `sb` -> (height, width, 4) float32."""
+    out = _prior_in(prior, camera.pixels)
+    t, n, m, s = _f32(sb["tris"], 16), _f32(sb["nodes"], 12), _f32(sb["mats"], 16), _f32(sb["spheres"], 8)
+    z = lambda a, c: a.reshape(-1) if a.size else np.zeros(c, np.float32)
+    rc = lib().pt_trace_camera_host(z(t, 16), len(t), z(n, 12), len(n), z(m, 16), len(m), z(s, 8), len(s), int(flags),
+                                    int(max_bounce), int(mode), C.byref(camera), int(frame_first), int(n_frames),
+                                    int(prior is not None), out.ctypes.data)
+    if rc:
+        raise PTError(rc, "pt_trace_camera_host: rejected scene or bad arguments")
+    return out.reshape(camera.height, camera.width, 4)
 
 
 def noise_host(moments, frames, target, in_footprint=None):
