@@ -549,6 +549,79 @@ int pt_camera_rays_host(const pt_camera* camera, const int* xy, long long n, int
  * pt_intersect_device (a depth buffer through the lens) or a pt_trace_device.  Needs no uploaded scene. */
 int pt_camera_rays_device(pt_ctx* ctx, const pt_camera* camera, int frame, void* d_rays, void* d_states);
 
+/* Film: the running image, the luminance moments and the first-hit guides of one pt_camera on one
+ * context, kept on the device and written in one pass over the paths -- what a camera-model render needs to be
+ * rendered to a noise level (pt_film_noise, pt_film_expose_until) and shown denoised meanwhile (pt_film_denoise).
+ *
+ * For a film of camera cam, width x height pixels, guide_frames = G >= 1, every plane bit for bit:
+ *   image    after pt_film_expose(F, N, A) what pt_trace_camera_device(cam, F, N, A, image) writes.
+ *   moments  (S1, S2) per pixel as in "Per-pixel noise estimate" above: for each frame of the call, in frame order,
+ *            Y of that frame's path colour (the colour that enters the running mean, not the mean), S1 += Y,
+ *            S2 += Y*Y.  An exposure with accumulate_first = 0 starts from (0, 0) and sets the film's frame count
+ *            n = N; with 1 it continues and n += N.
+ *   guides   two quads per pixel, (N.rgb, Z) and (A.rgb, 0).  N, A and Z are the rgb, rgb and .x of
+ *            pt_trace_camera(cam, 1, G, 0) on a context whose display mode is 2, 3 and 4 (same scene, flags and
+ *            max_bounce): functions of a path's first segment, which the exposure that passes through a frame
+ *            f <= G takes from the first hit it casts anyway.  The context's own display mode governs the radiance
+ *            only, never the guides.  The film keeps guides_held, the largest h such that frames 1..h are folded in
+ *            (h <= G): an exposure whose range contains frame h + 1 raises h to min(G, its last frame); any other
+ *            leaves the guides alone.  They do not depend on accumulate_first and are reset (h = 0) only by
+ *            pt_film_set_camera, by another guide_frames, or when the context's scene has been replaced.
+ * One ray per pixel; a row-split context answers for the whole width x height, like a trace.
+ *
+ * A film is invisible to rendering, as a query and a trace are: no timing events, launch counters, tile order,
+ * context moments or captured graph.  Everything is enqueued on the context's stream (pt_stream); only create and
+ * destroy allocate.  Errors follow pt_trace_camera's: PT_E_STATE before pt_upload_scene; PT_E_ARG for frame ranges,
+ * flags and null pointers. */
+typedef struct pt_film pt_film;
+/* width * height must be below 2^31.  The film starts black, n = 0, guides_held = 0.  Needs no uploaded scene. */
+int pt_film_create(pt_ctx* ctx, const pt_camera* camera, int guide_frames, pt_film** out);
+/* Waits for the context's stream.  Before pt_destroy of its context. */
+void pt_film_destroy(pt_film* film);
+/* Another camera of the same width x height (else PT_E_ARG); guides_held = 0.  The image and the moments stay the
+ * caller's business, as on a context: the next exposure with accumulate_first = 0 restarts them. */
+int pt_film_set_camera(pt_film* film, const pt_camera* camera);
+/* Frames frame_first .. frame_first + n_frames - 1 of every pixel.  Enqueued, not waited for. */
+int pt_film_expose(pt_film* film, int frame_first, int n_frames, int accumulate_first);
+/* The summary of every pixel, q = quantise(S1, S2, n), pixels = width * height, reduced on the device (integers
+ * only: exact in any order).  Waits.  PT_E_STATE: n < 2. */
+int pt_film_noise(pt_film* film, float target, pt_noise_stats* out);
+/* pt_render_until's rule on a film: exposes `batch` frames at a time (the first batch with the caller's
+ * accumulate_first, the rest accumulating; the last batch may be shorter) and stops after the first batch with
+ * sum_q <= (unsigned)(target * 65536.0f) * pixels, or after max_frames.  The image afterwards is that of
+ * pt_film_expose(frame_first, *frames_done, accumulate_first), bit for bit.  `last` may be NULL.
+ * PT_E_ARG: batch < 2, max_frames < batch or target <= 0. */
+int pt_film_expose_until(pt_film* film, int frame_first, int accumulate_first, int batch, int max_frames,
+                         float target, int* frames_done, pt_noise_stats* last);
+/* pt_denoise's filter on the film's planes, the whole image its footprint: guided by the variance of the mean
+ * luminance when n >= 2.  If guides_held < params->guide_frames the guides are completed first by a guides-only
+ * launch of frames guides_held + 1 .. G, whose paths end after the first segment and which touches neither the image
+ * nor the moments; a guide_frames other than the film's becomes the film's and re-gathers them.  Enqueued, not waited
+ * for.  params NULL = pt_denoise_defaults (guide_frames 4); info may be NULL (guides_rendered: that launch ran). */
+int pt_film_denoise(pt_film* film, const pt_denoise_params* params, pt_denoise_info* info);
+/* n and guides_held (0 after the context's scene was replaced).  Either pointer may be NULL. */
+int pt_film_info(pt_film* film, int* frames, int* guides_held);
+#define PT_FILM_IMAGE 0          /* W*H*4 float */
+#define PT_FILM_MOMENTS 1        /* W*H*2 float */
+#define PT_FILM_GUIDES 2         /* W*H*8 float, pt_read_guides' order */
+#define PT_FILM_DENOISED 3       /* W*H*4 float; PT_E_STATE before a denoise */
+#define PT_FILM_IMAGE_ACES8 4    /* W*H*4 bytes, the ACES view computed on the device */
+#define PT_FILM_DENOISED_ACES8 5
+/* Waits for the context's stream, then copies the plane.  PT_E_ARG: bytes is not the plane's size. */
+int pt_film_read(pt_film* film, int what, void* host_dst, size_t bytes);
+/* The device planes 0..3, for a client's own kernels on the context's stream.  On the device the guides are two
+ * planes, not interleaved: (N.rgb, Z) of every pixel, then (A.rgb, 0) of every pixel. */
+int pt_film_device(pt_film* film, int what, void** dev_ptr, size_t* bytes);
+/* An exposure on the host, of a scene in pt_upload_scene's arrays: packs it as pt_upload_scene does and runs the
+ * device kernel's own per-pixel code.  No device is touched.  rgba (W*H*4), moments (W*H*2) and guides (W*H*8, as
+ * PT_FILM_GUIDES) are in and out; frames_before (>= 0) and guides_held (0..guide_frames) are the film's n and h before
+ * the call, *guides_held_out (may be NULL) is h after it.  Returns the packer's error for a rejected scene. */
+int pt_film_expose_host(const float* tris, int n_tris, const float* bvh, int n_nodes, const float* mats, int n_mats,
+                        const float* spheres, int n_spheres, int ctx_flags, int max_bounce, int display_mode,
+                        const pt_camera* camera, int guide_frames, int frame_first, int n_frames, int accumulate_first,
+                        int frames_before, int guides_held, float* rgba, float* moments, float* guides,
+                        int* guides_held_out);
+
 #ifdef __cplusplus
 }
 #endif

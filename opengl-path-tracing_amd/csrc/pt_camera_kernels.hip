@@ -13,7 +13,8 @@
 // again, where k_trace reloads two quads.  The kernel reads nothing but the scene and an accumulating call's prior,
 // and writes one quad per pixel.  M: the model as a template constant, or -1 for the launch-uniform switch that ships
 // (DESIGN.md §14.4).
-// TWIN: k_trace<false, true> (pt_trace_kernels.hip), the refill loop.
+// TWIN: k_trace<false, true> (pt_trace_kernels.hip), the refill loop; and k_film_expose (pt_film_kernels.hip), which
+// restates this one.
 #include "pt_camera_launch.h"
 #include "pt_scene_pack.h"
 

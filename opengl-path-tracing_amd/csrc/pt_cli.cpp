@@ -84,7 +84,12 @@ static void usage() {
                  "                  what --pick finds under that pixel, in binary32) for thinlens; --ortho-width W (world\n"
                  "                  width of the view) for ortho; --no-aa: no jitter.  One context only: not with --gpus\n"
                  "                  above 1, --ranks, --adaptive, --noise-target, --denoise*, --events, --checkpoint,\n"
-                 "                  --resume, --rays, --hits, --radiance or --seeds\n");
+                 "                  --resume, --rays, --hits, --radiance or --seeds\n"
+                 "  --film          with --camera-model: the frames go through a film (pt_api.h: pt_film), which keeps\n"
+                 "                  moments and first-hit guides of that camera beside the image, so that --noise-target X\n"
+                 "                  [--batch B] [--max-spp N] (pt_film_expose_until) and --denoise [--denoise-iters N]\n"
+                 "                  [--guide-frames G] [--denoise-pfm F] [--denoise-ppm F] (pt_film_denoise) work, and\n"
+                 "                  --pfm, --ppm and --json are of the film's planes; --json gains a \"film\" object\n");
 }
 
 // Checkpoint of a progressive render (SURVEY.md §5 checkpoint / resume): the running mean
@@ -225,6 +230,8 @@ int main(int argc, char** argv) {
     int cam_model = -1;                   // >= 0: render through pt_trace_camera
     pt_camera pcam = {PT_CAM_PINHOLE, 0, 0, 0, {0}, 0.0f, 1.0f, 1.0f, 0.0f};
     bool focus_at = false, lens_given = false, ranks_given = false;
+    bool use_film = false;                // the camera model's frames go through a pt_film
+    int film_frames = 0, film_held = 0;
     int focus_xy[2] = {0, 0};
     for (int i = 3; i < argc; i++) {
         std::string a = argv[i];
@@ -281,17 +288,24 @@ int main(int argc, char** argv) {
         }
         else if (a == "--ortho-width") { pcam.ortho_width = (float)std::atof(next()); lens_given = true; }
         else if (a == "--no-aa") { pcam.flags |= PT_CAM_NO_AA; lens_given = true; }
+        else if (a == "--film") use_film = true;
         else { usage(); return 2; }
     }
     if (ranks == 0) ranks = gpus;
+    if (use_film && cam_model < 0) {
+        std::fprintf(stderr, "--film needs --camera-model\n");
+        return 2;
+    }
     if (cam_model < 0 && lens_given) {
         std::fprintf(stderr, "--aperture, --focus, --focus-at, --ortho-width and --no-aa need --camera-model\n");
         return 2;
     }
     if (cam_model >= 0) {
         // one context, frames 1..spp, nothing that owns the render loop or the traced-ray options
+        // (a film brings the moments and the guides of the camera model: --noise-target and --denoise work on it)
         const char* clash = gpus > 1 ? "--gpus above 1" : ranks_given ? "--ranks" : adaptive ? "--adaptive"
-                          : until ? "--noise-target" : (denoise || !denoise_pfm.empty() || !denoise_ppm.empty()) ? "--denoise"
+                          : (until && !use_film) ? "--noise-target"
+                          : ((denoise || !denoise_pfm.empty() || !denoise_ppm.empty()) && !use_film) ? "--denoise"
                           : events ? "--events" : !checkpoint.empty() ? "--checkpoint" : !resume.empty() ? "--resume"
                           : !rays_path.empty() ? "--rays" : !hits_path.empty() ? "--hits" : !radiance_path.empty() ? "--radiance"
                           : !seeds_path.empty() ? "--seeds" : nullptr;
@@ -479,6 +493,7 @@ int main(int argc, char** argv) {
     auto t1 = std::chrono::steady_clock::now();
     int frames_run = 0, resets = 0;
     pt_noise_stats noise = {0, 0, 0, 0, 0};
+    pt_film* film = nullptr;
     if (events) {
         // the reference's render loop (ogl_path_trace.h:160-204) driven by a recorded session
         std::vector<Event> ev;
@@ -504,7 +519,7 @@ int main(int argc, char** argv) {
         }
         pt_viewer_destroy(view);
         spp = frames_run;
-    } else if (until) {
+    } else if (until && !use_film) {
         // frames 1.. in batches until the noise summary meets the target (or max_spp frames)
         int done = 0;
         if (adaptive) {     // ... each tile until it meets the target on its own
@@ -550,12 +565,28 @@ int main(int argc, char** argv) {
             pcam.focus = ((h.p[0] - cam[0]) * fx + (h.p[1] - cam[1]) * fy) + (h.p[2] - cam[2]) * fz;
             std::printf("focus at pixel (%d, %d): %.9g\n", focus_xy[0], focus_xy[1], pcam.focus);
         }
-        std::vector<float> cimg(4 * (size_t)W * H, 0.0f);
-        for (int k = 0; k < spp; k += chunk) {
-            const int n = std::min(chunk, spp - k), f0 = 1 + k;
-            CHECK(pt_trace_camera(ctx[0], &pcam, f0, n, f0 == 1 ? 0 : 1, cimg.data()), ctx[0]);
+        if (use_film) {
+            // ... through a film: the image, the moments and the guides of this camera stay on the device
+            CHECK(pt_film_create(ctx[0], &pcam, dparams.guide_frames, &film), ctx[0]);
+            if (until) {
+                int done = 0;
+                CHECK(pt_film_expose_until(film, 1, 0, batch, max_spp, noise_target, &done, &noise), ctx[0]);
+                spp = done;
+            } else {
+                for (int k = 0; k < spp; k += chunk) {
+                    const int n = std::min(chunk, spp - k), f0 = 1 + k;
+                    CHECK(pt_film_expose(film, f0, n, f0 == 1 ? 0 : 1), ctx[0]);
+                }
+                if (spp >= 2) CHECK(pt_film_noise(film, 0.0f, &noise), ctx[0]);
+            }
+        } else {
+            std::vector<float> cimg(4 * (size_t)W * H, 0.0f);
+            for (int k = 0; k < spp; k += chunk) {
+                const int n = std::min(chunk, spp - k), f0 = 1 + k;
+                CHECK(pt_trace_camera(ctx[0], &pcam, f0, n, f0 == 1 ? 0 : 1, cimg.data()), ctx[0]);
+            }
+            CHECK(pt_write_rgba32f(ctx[0], cimg.data(), cimg.size() * 4), ctx[0]);
         }
-        CHECK(pt_write_rgba32f(ctx[0], cimg.data(), cimg.size() * 4), ctx[0]);
     } else {
         for (int k = 0; k < spp; k += chunk) {
             const int n = std::min(chunk, spp - k), f0 = first + k;
@@ -590,7 +621,21 @@ int main(int argc, char** argv) {
     }
     std::vector<float> dimg;
     std::vector<unsigned char> drgba;
-    if (denoise) {    // the filtered view of the finished image (the image itself stays as rendered)
+    if (film) {       // the film's planes, not the context's image
+        CHECK(pt_film_read(film, PT_FILM_IMAGE, img.data(), img.size() * 4), ctx[0]);
+        CHECK(pt_film_read(film, PT_FILM_IMAGE_ACES8, rgba.data(), rgba.size()), ctx[0]);
+        if (denoise) {
+            auto td = std::chrono::steady_clock::now();
+            CHECK(pt_film_denoise(film, &dparams, &dinfo), ctx[0]);
+            dimg.assign(4 * (size_t)W * H, 0.0f);
+            drgba.assign(4 * (size_t)W * H, 0);
+            CHECK(pt_film_read(film, PT_FILM_DENOISED, dimg.data(), dimg.size() * 4), ctx[0]);
+            denoise_ms = std::chrono::duration<double>(std::chrono::steady_clock::now() - td).count() * 1e3;
+            CHECK(pt_film_read(film, PT_FILM_DENOISED_ACES8, drgba.data(), drgba.size()), ctx[0]);
+        }
+        CHECK(pt_film_info(film, &film_frames, &film_held), ctx[0]);
+        pt_film_destroy(film);
+    } else if (denoise) {    // the filtered view of the finished image (the image itself stays as rendered)
         auto td = std::chrono::steady_clock::now();
         CHECK(pt_denoise(ctx[0], &dparams, &dinfo), ctx[0]);
         denoise_ms = std::chrono::duration<double>(std::chrono::steady_clock::now() - td).count() * 1e3;
@@ -625,6 +670,13 @@ int main(int argc, char** argv) {
         if (until)
             std::printf(", \"frames_done\": %d, \"noise_mean\": %.8f, \"noise_max\": %.8f, \"noise_above_frac\": %.8f",
                         spp, (double)noise.sum_q / npx / 65536.0, noise.max_q / 65536.0, (double)noise.above / npx);
+        if (use_film) {
+            std::printf(", \"film\": {\"frames\": %d, \"guides_held\": %d", film_frames, film_held);
+            if (film_frames >= 2)
+                std::printf(", \"noise_mean\": %.8f, \"noise_max\": %.8f, \"sum_q\": %llu, \"pixels\": %llu",
+                            (double)noise.sum_q / npx / 65536.0, noise.max_q / 65536.0, noise.sum_q, noise.pixels);
+            std::printf("}");
+        }
         if (adaptive)
             std::printf(", \"tiles\": %llu, \"tiles_active\": %llu, \"pixel_frames\": %llu", astats.tiles,
                         astats.tiles_active, astats.pixel_frames);

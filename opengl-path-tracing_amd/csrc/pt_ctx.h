@@ -22,6 +22,7 @@ struct pt_ctx {
     ptl::SceneFacts sf;             // what ptp::pack_scene learned (the launch planner's input)
     ptl::Tuning tun;                // pt_set_tuning values and the kernel variant
     bool scene_ok = false, cam_ok = false, counting = false;
+    unsigned long long scene_serial = 0;   // moves whenever the device scene is replaced (pt__scene_serial: a film's guides)
     float cam[12] = {0};
     std::string err;
     // ---- the image and its launches (pt_render.hip)

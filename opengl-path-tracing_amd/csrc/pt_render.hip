@@ -234,6 +234,7 @@ int pt_upload_scene(pt_ctx* c, const float* tris, int n_tris, const float* bvh, 
     }
     c->sf = packed.facts;
     c->scene_ok = true;
+    c->scene_serial++;
     return PT_OK;
 }
 
@@ -876,6 +877,7 @@ int pt__aces_launch(const void* src, void* dst, long long n, void* stream) {
 int pt__scene_set_ready(pt_ctx* c, int ready) {
     if (!c) return PT_E_ARG;
     c->scene_ok = ready != 0 && c->d_scene[ptp::kMats] != nullptr;
+    if (c->scene_ok) c->scene_serial++;       // a group's upload: the buffers were filled behind pt_upload_scene's back
     return PT_OK;
 }
 
@@ -905,6 +907,14 @@ int pt__trace_view(const pt_ctx* c, ptt::CtxView* out) {
     if (rc) return rc;
     out->mats = c->d_scene[ptp::kMats];
     out->max_bounce = c->cfg.max_bounce, out->mode = c->cfg.display_mode;
+    return PT_OK;
+}
+
+// The scene serial (pt_film_kernels.hip; internal, not part of the public ABI): a count that moves whenever the device
+// scene is replaced, so that a film knows its guides are of another scene.  Changes nothing in the context.
+int pt__scene_serial(const pt_ctx* c, unsigned long long* out) {
+    if (!c || !out) return PT_E_ARG;
+    *out = c->scene_serial;
     return PT_OK;
 }
 

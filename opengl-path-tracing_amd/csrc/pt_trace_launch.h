@@ -39,4 +39,6 @@ hipError_t launch_trace(hipStream_t s, const CtxView& v, const Launch& l);
 extern "C" {
 // pt_render.hip, not part of the public ABI: the view of a context, changing nothing in it.
 int pt__trace_view(const pt_ctx* c, ptt::CtxView* out);
+// ... and the count of scene replacements (pt_upload_scene bumps it on success): what a film's guides depend on.
+int pt__scene_serial(const pt_ctx* c, unsigned long long* out);
 }

@@ -228,6 +228,18 @@ def lib():
             "pt_trace_camera_host": (ip, [_F, ip, _F, ip, _F, ip, _F, ip, ip, ip, ip, C.POINTER(Camera), ip, ip, ip, vp]),
             "pt_camera_rays_host": (ip, [C.POINTER(Camera), vp, C.c_longlong, ip, vp, vp]),
             "pt_camera_rays_device": (ip, [vp, C.POINTER(Camera), ip, vp, vp]),
+            "pt_film_create": (ip, [vp, C.POINTER(Camera), ip, C.POINTER(vp)]),
+            "pt_film_destroy": (None, [vp]),
+            "pt_film_set_camera": (ip, [vp, C.POINTER(Camera)]),
+            "pt_film_expose": (ip, [vp, ip, ip, ip]),
+            "pt_film_noise": (ip, [vp, fp, C.POINTER(NoiseStats)]),
+            "pt_film_expose_until": (ip, [vp, ip, ip, ip, ip, fp, C.POINTER(ip), C.POINTER(NoiseStats)]),
+            "pt_film_denoise": (ip, [vp, C.POINTER(DenoiseParams), C.POINTER(DenoiseInfo)]),
+            "pt_film_info": (ip, [vp, C.POINTER(ip), C.POINTER(ip)]),
+            "pt_film_read": (ip, [vp, ip, vp, C.c_size_t]),
+            "pt_film_device": (ip, [vp, ip, C.POINTER(vp), C.POINTER(C.c_size_t)]),
+            "pt_film_expose_host": (ip, [_F, ip, _F, ip, _F, ip, _F, ip, ip, ip, ip, C.POINTER(Camera), ip, ip, ip, ip, ip,
+                                         ip, _F, _F, _F, C.POINTER(ip)]),
             "pt_group_create": (ip, [C.POINTER(vp), ip, C.POINTER(vp)]),
             "pt_group_destroy": (None, [vp]),
             "pt_group_last_error": (C.c_char_p, [vp]),
@@ -1042,6 +1054,107 @@ def trace_camera_host(sb, camera, frame_first=1, n_frames=1, prior=None, flags=0
     if rc:
         raise PTError(rc, "pt_trace_camera_host: rejected scene or bad arguments")
     return out.reshape(camera.height, camera.width, 4)
+
+
+# ----------------------------------------------------------------------------- film
+PT_FILM_IMAGE, PT_FILM_MOMENTS, PT_FILM_GUIDES, PT_FILM_DENOISED, PT_FILM_IMAGE_ACES8, PT_FILM_DENOISED_ACES8 = range(6)
+FILM_PLANES = {"image": (PT_FILM_IMAGE, 4, np.float32), "moments": (PT_FILM_MOMENTS, 2, np.float32),
+               "guides": (PT_FILM_GUIDES, 8, np.float32), "denoised": (PT_FILM_DENOISED, 4, np.float32),
+               "image_aces8": (PT_FILM_IMAGE_ACES8, 4, np.uint8), "denoised_aces8": (PT_FILM_DENOISED_ACES8, 4, np.uint8)}
+
+
+class Film:
+    """pt_film (include/pt_api.h): the running image, luminance moments and first-hit guides of one
+    Camera on one PathTracer, on the device.  Close it before its tracer."""
+
+    def __init__(self, tracer, camera, guide_frames=4):
+        self.pt, self.camera, self.guide_frames = tracer, camera, int(guide_frames)
+        self.h = C.c_void_p()
+        tracer._check(lib().pt_film_create(tracer.h, C.byref(camera), self.guide_frames, C.byref(self.h)))
+
+    def _check(self, rc):
+        self.pt._check(rc)
+
+    def close(self):
+        if self.h:
+            lib().pt_film_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def set_camera(self, camera):
+        """Another Camera of the same size; the guides are gathered anew."""
+        self._check(lib().pt_film_set_camera(self.h, C.byref(camera)))
+        self.camera = camera
+
+    def expose(self, frame_first=1, n_frames=1, accumulate_first=0):
+        """pt_film_expose: enqueued on the tracer's stream, not waited for."""
+        self._check(lib().pt_film_expose(self.h, int(frame_first), int(n_frames), int(accumulate_first)))
+
+    def expose_until(self, target, batch=16, max_frames=1024, frame_first=1, accumulate_first=0):
+        """pt_film_expose_until -> (frames_done, summary dict)."""
+        done, s = C.c_int(), NoiseStats()
+        self._check(lib().pt_film_expose_until(self.h, int(frame_first), int(accumulate_first), int(batch),
+                                               int(max_frames), float(target), C.byref(done), C.byref(s)))
+        return done.value, s.as_dict()
+
+    def noise(self, target):
+        """pt_film_noise: the integer noise summary of every pixel as a dict (NoiseStats.as_dict)."""
+        s = NoiseStats()
+        self._check(lib().pt_film_noise(self.h, float(target), C.byref(s)))
+        return s.as_dict()
+
+    def denoise(self, **params):
+        """pt_film_denoise.  params: fields of pt_denoise_params over its defaults, guide_frames defaulting to the
+        film's.  -> dict(guided, guides_rendered, iterations, frames)."""
+        params.setdefault("guide_frames", self.guide_frames)
+        p, info = denoise_params(**params), DenoiseInfo()
+        self._check(lib().pt_film_denoise(self.h, C.byref(p), C.byref(info)))
+        self.guide_frames = int(p.guide_frames)
+        return dict(guided=bool(info.guided), guides_rendered=bool(info.guides_rendered),
+                    iterations=int(info.iterations), frames=int(info.frames))
+
+    def info(self):
+        """-> (frames in the moments, guides_held)."""
+        n, h = C.c_int(), C.c_int()
+        self._check(lib().pt_film_info(self.h, C.byref(n), C.byref(h)))
+        return n.value, h.value
+
+    def read(self, what="image"):
+        """pt_film_read of a plane of FILM_PLANES (a name or a PT_FILM_* value) -> (height, width, k) array."""
+        if not isinstance(what, str):
+            what = [k for k, v in FILM_PLANES.items() if v[0] == int(what)][0]
+        code, k, dtype = FILM_PLANES[what]
+        out = np.zeros((self.camera.height, self.camera.width, k), dtype)
+        self._check(lib().pt_film_read(self.h, code, out.ctypes.data, out.nbytes))
+        return out
+
+    def device(self, what="image"):
+        """pt_film_device -> (device pointer, bytes) of one of the planes image, moments, guides, denoised."""
+        p, n = C.c_void_p(), C.c_size_t()
+        self._check(lib().pt_film_device(self.h, FILM_PLANES[what][0], C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+
+def film_expose_host(sb, camera, guide_frames, frame_first=1, n_frames=1, accumulate_first=0, state=None, flags=0,
+                     max_bounce=5, mode=1):
+    """pt_film_expose_host: an exposure on the host (no device) -- the per-pixel code is the device kernel's own.
+    state: what an earlier call returned, or None for a new film -> dict(image (H, W, 4), moments (H, W, 2), guides
+    (H, W, 8), frames, guides_held)."""
+    h, w = camera.height, camera.width
+    if state is None:
+        state = dict(image=np.zeros((h, w, 4), np.float32), moments=np.zeros((h, w, 2), np.float32),
+                     guides=np.zeros((h, w, 8), np.float32), frames=0, guides_held=0)
+    img, mom, gd = (np.array(state[k], np.float32) for k in ("image", "moments", "guides"))
+    t, n, m, s = _f32(sb["tris"], 16), _f32(sb["nodes"], 12), _f32(sb["mats"], 16), _f32(sb["spheres"], 8)
+    z = lambda a, c: a.reshape(-1) if a.size else np.zeros(c, np.float32)
+    held = C.c_int()
+    rc = lib().pt_film_expose_host(z(t, 16), len(t), z(n, 12), len(n), z(m, 16), len(m), z(s, 8), len(s), int(flags),
+                                   int(max_bounce), int(mode), C.byref(camera), int(guide_frames), int(frame_first),
+                                   int(n_frames), int(accumulate_first), int(state["frames"]), int(state["guides_held"]),
+                                   img.reshape(-1), mom.reshape(-1), gd.reshape(-1), C.byref(held))
+    if rc:
+        raise PTError(rc, "pt_film_expose_host: rejected scene or bad arguments")
+    frames = state["frames"] + n_frames if accumulate_first else n_frames
+    return dict(image=img, moments=mom, guides=gd, frames=frames, guides_held=held.value)
 
 
 def noise_host(moments, frames, target, in_footprint=None):
