@@ -168,6 +168,22 @@ PT_HD float tri_plane(Q nd, f3 o, f3 d) {    // nd: quad 0 {n, d0}
     return -(pt::dot(n, o) + nd.w) / pt::dot(n, d);
 }
 
+// The plane-window filter of a leaf pair at a segment's initial t0 ("Round 20"): whether a leaf
+// visit of the pair could do more than clear its candidate bit.  The operations of the leaf phase's plane tests
+// (leaf_pair_tests, pt_render_sm.h) in their order, so the same bits: the pair's 2-way choice depends on a triangle
+// only when its plane distance is in (1e-4, t) for the first or [1e-4, t) for the second; outside both, h1 and h2
+// cannot pass win_open and nothing moves.  Both windows only shrink while a segment runs (t never grows, 1e-4 is
+// fixed), so a pair outside them at t0 is outside them at every later visit, and dropping its bit at set-up gives
+// the same (t, triangle).  NaN and +-inf distances (a zero denominator) fail every compare: outside.
+// nda / ndb: quad 0 {n, d0} of the pair's slots s0 / s0 + 1 (the slot's own quad, not the hit triangle's: a coplanar
+// pair's two quads may differ in the sign of zero components); cop: the pair's coplanar flag (ndb is not read).
+template <class Q>
+PT_HD bool pair_in_window(Q nda, Q ndb, bool cop, f3 o, f3 d, float t0) {
+    const float ta = tri_plane(nda, o, d);
+    const float tb = cop ? ta : tri_plane(ndb, o, d);
+    return pt::win_open(ta, t0) | pt::win_closed(tb, t0);
+}
+
 // ACES film tonemap (screenQuadFrag.c:12-26) of one pixel -> RGBA8, alpha 255.
 // (U4: the kernels' uchar4, or any struct of four unsigned char)
 template <class U4, class Q>

@@ -49,6 +49,25 @@
 #define PT_POOL_SWEEP_SIGNED 1
 #endif
 #define PT_POOL_SIGNED_ON (PT_POOL_SWEEP_SIGNED && PT_POOL_SWEEP_LDS && PT_POOL_SWEEP_DEPTH > 0)
+// Round 20: a bounce ray starts on the triangle it left, so its own pair's plane distance is near
+// zero and, unless the pair is not coplanar, outside both hit windows for the whole segment.  Such a visit changes
+// nothing but `bi &= bi - 1` and still costs the path a LEAF pass slot.  The thin wall boxes fall to the sweep's window
+// clause; the fat boxes of the rotated blocks and non-coplanar pairs do not.  The set-up pass runs the LEAF pass's own
+// plane tests on that one pair (pti::pair_in_window, pt_isect.h: the quads are staged already) and clears its bit
+// where both distances are outside their windows at t0: the same (t, triangle) bit for bit, since the windows only
+// shrink.  Camera rays and sphere hits have no own pair.  k_render_sm keeps its code: tests/test_gpu_path_pool.py and
+// tests/test_gpu_plane_filter.py compare the two kernels word for word, which is the check of this filter.
+// CPU model on Cornell's 1080p paths (tests/pool/plane_window_sim.cpp): 1.43 candidate visits per segment, 0.30 of
+// them the own pair outside its windows, 20.9% of the LEAF path-visits.
+//   PT_POOL_PLANE_FILTER 1: the filter; 0: every candidate bit is visited, for the same-process A/B
+//                        (profiles/ab/r20_plane_window/)
+// Same-process A/B against the parent (a copy of it: -0.58% and -0.03%): +2.76% on C2's 1024-frame launch, +2.64% on
+// the 1080p/8 share; with both plane distances computed and selected by the coplanar flag +2.33%, so the second
+// triangle's read and division sit under a wave-uniform branch.  36 VALU, two LDS reads and one division per set-up
+// pass on Cornell; 94 VGPRs (93).  LDS instructions per segment 1.202 -> 1.122, wave-VALU 21.69 -> 21.27.
+#ifndef PT_POOL_PLANE_FILTER
+#define PT_POOL_PLANE_FILTER 1
+#endif
 namespace {
 
 // The reference walk and leaf tests for a ray outside the exact-reciprocal guard (a few thousand of C2's segments),
@@ -174,11 +193,17 @@ __global__ __launch_bounds__(NT, MINW) void k_render_pool(KParams p) {
             unsigned pcost = cost_of(__float_as_uint(c4.w));
             bool report = cost_report(__float_as_uint(c4.w));
             bool retired = false;
+#if PT_POOL_PLANE_FILTER
+            int own = -1;              // the pair of the triangle a continuing path's ray leaves (round 20)
+#endif
             if (on && !(t < 0.0f)) {   // a finished segment (t < 0: fresh)
                 const bool hit = hprim != -1;
                 pcost++;
                 f3 rgb;
                 const bool finished = shade_segment<true>(F, p, S, hit, hprim, t, o, d, inc, col, state, bounce, rgb);
+#if PT_POOL_PLANE_FILTER
+                if (!finished & (hprim >= 0)) own = hprim >> 1;
+#endif
                 if (finished) {
                     bounce = -1;
                     const f3 px = (mk(0, 0, 0) + rgb) / 1.0f;
@@ -237,17 +262,35 @@ __global__ __launch_bounds__(NT, MINW) void k_render_pool(KParams p) {
                 }
                 const bool walk = !ray_has_nan(o, d);     // (a sweeping launch has nodes and triangles)
 #if PT_POOL_SIGNED_ON
-                const unsigned cand = sweep_candidates_signed<PT_POOL_SWEEP_DEPTH>(p, S, signed_pairs, walk & fast_seg, o, rd, t);
+                unsigned cand = sweep_candidates_signed<PT_POOL_SWEEP_DEPTH>(p, S, signed_pairs, walk & fast_seg, o, rd, t);
 #elif PT_POOL_SWEEP_DEPTH > 0 && PT_POOL_SWEEP_LDS
-                const unsigned cand = sweep_candidates<PT_POOL_SWEEP_DEPTH>(p, S, boxes, walk & fast_seg, o, rd, t);
+                unsigned cand = sweep_candidates<PT_POOL_SWEEP_DEPTH>(p, S, boxes, walk & fast_seg, o, rd, t);
 #else
-                const unsigned cand = sweep_candidates<PT_POOL_SWEEP_DEPTH>(p, S, sweep_tab, walk & fast_seg, o, rd, t);
+                unsigned cand = sweep_candidates<PT_POOL_SWEEP_DEPTH>(p, S, sweep_tab, walk & fast_seg, o, rd, t);
 #endif
                 // rays outside the guard: cold code, the whole reference walk here (wave-uniform branch)
                 const bool cold = walk & !fast_seg;
                 if (__any(cold)) {
                     if (cold) pool_cold_walk(p, S, o, d, t, hprim);
                 }
+#if PT_POOL_PLANE_FILTER
+                // the own pair's plane tests at t0, as its LEAF visit would run them (a ray outside the guard has no bit)
+                if ((own >= 0) & (((cand >> (own & 31)) & 1u) != 0u)) {
+                    const int s0 = 2 * own;
+                    const bool cop = __float_as_int(tri_quad<true>(S, s0 + 1, 1).w) != 0;
+                    const float4 nda = tri_quad<true>(S, s0, 0);
+                    // the second triangle's read and division only where some lane's pair is not coplanar
+                    // (wave-uniform, as leaf_pair_tests has it: Cornell has no such pair)
+                    bool keep;
+                    if (__any(!cop)) {
+                        const float4 ndb = cop ? nda : tri_quad<true>(S, s0 + 1, 0);
+                        keep = pti::pair_in_window(nda, ndb, cop, o, d, t);
+                    } else {
+                        keep = pti::pair_in_window(nda, nda, true, o, d, t);
+                    }
+                    if (!keep) cand &= ~(1u << own);
+                }
+#endif
                 bi = cand;
                 to_leaf = cand != 0u;
             }
