@@ -14,21 +14,24 @@
 // and writes one quad per pixel.  M: the model as a template constant, or -1 for the launch-uniform switch that ships
 // (DESIGN.md §14.4).
 // TWIN: k_trace<false, true> (pt_trace_kernels.hip), the refill loop; and k_film_expose (pt_film_kernels.hip), which
-// restates this one.
+// restates this one (one shared loop moved the registers of all three kernels).
+// Shared with the other ray-batch units: the scene accessor, rank_in, the argument-segment read and the
+// persistent grid's size come from pt_batch_device.h, the error return, the checks and the staged buffer of the entry
+// points from pt_entry.h.
+#include "pt_batch_device.h"
 #include "pt_camera_launch.h"
+#include "pt_entry.h"
 #include "pt_scene_pack.h"
 
-#include <climits>
 #include <cstddef>
-#include <string>
 #include <type_traits>
 
 namespace ptcam {
 namespace {
 
-constexpr int kThreads = 256;              // a workgroup: 4 waves
-constexpr int kWaves = kThreads / 64;
-constexpr int kMaxDevices = 64;
+using ptb::kThreads;
+using ptb::kWaves;
+using ptb::rank_in;
 constexpr int kKernels = 5;                // the switch and the four models
 
 struct CamArgs {
@@ -44,52 +47,12 @@ struct CamArgs {
     Prepared cam;
 };
 
-// TWIN: DevScene<false> (pt_trace_kernels.hip).
-struct DevScene {
-    const CamArgs& a;
-    __device__ __forceinline__ int n_nodes() const { return a.n_nodes; }
-    __device__ __forceinline__ int n_spheres() const { return a.n_spheres; }
-    __device__ __forceinline__ bool scene_fast() const { return a.scene_fast != 0; }
-    __device__ __forceinline__ void node(int i, float4& lo, float4& hi) const {
-        lo = a.nodes[2 * (size_t)i];
-        hi = a.nodes[2 * (size_t)i + 1];
-    }
-    __device__ __forceinline__ float4 tri(int slot, int k) const { return a.tris[4 * (size_t)slot + k]; }
-    __device__ __forceinline__ float4 sphere(int i, int k) const { return a.spheres[2 * (size_t)i + k]; }
-    __device__ __forceinline__ float4 leaf_tris(int pair) const { return a.leaf_tris[pair]; }
-    __device__ __forceinline__ float4 mat(int i, int k) const { return a.mats[3 * (size_t)i + k]; }
-};
-
-// Number of set bits of m below this lane.
-__device__ __forceinline__ int rank_in(unsigned long long m) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
-
-// The camera, read from the kernel's argument segment where a ray is made, by vector loads (every lane the same
-// words): nothing of it is live during the walk.  Read as a by-value argument it stayed in SGPRs across the whole loop,
-// the kernel needed 106 SGPRs (112 allocated) against k_trace's 96, and a SIMD then held 6 of its waves, not the 7 the
-// runtime's occupancy query reports: the last seventh of the persistent grid ran as a tail, 28% slower on both scenes
-// measured (one session's measurement, with the grid-cap comparison that located it).  Scalar loads
-// at this place still peaked at 98 to 106.  The empty asm makes the address opaque and per-lane, so the loads are
-// neither hoisted out of the loop nor turned back into scalar ones.
-// Relies on CamArgs being the kernel's first and only parameter, so that it starts the argument segment (asserted
-// below the kernel) -- and on nothing else: should the compiler one day see through the asm, the result is the same
-// words from the same place, only with more SGPRs again (the resource table of tools/camera_measure.py shows it).
-// The kernel reads a.cam.W directly beside this copy: the one word it needs at every take and store stays a scalar.
-__device__ __forceinline__ Prepared load_camera() {
-    typedef const __attribute__((address_space(4))) uint32_t* kernarg_words;
-    static_assert(offsetof(CamArgs, cam) % 4 == 0 && sizeof(Prepared) % 4 == 0, "the camera is whole words");
-    kernarg_words w = (kernarg_words)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(CamArgs, cam) / 4;
-    asm volatile("" : "+v"(w));
-    union { Prepared cam; uint32_t u[sizeof(Prepared) / 4]; } c;
-#pragma unroll
-    for (int k = 0; k < (int)(sizeof(Prepared) / 4); k++) c.u[k] = w[k];
-    return c.cam;
-}
+// The camera, read back from the argument segment where a ray is made (ptb::load_arg has the why).
+__device__ __forceinline__ Prepared load_camera() { return ptb::load_arg<Prepared, offsetof(CamArgs, cam)>(); }
 
 template <int M>
 __global__ __launch_bounds__(kThreads) void k_trace_camera(CamArgs a) {
-    const DevScene sc = {a};
+    const ptb::DevScene<CamArgs> sc = {a};
     const ptt::Frames fr = a.fr;
     // the wave's share: cursor position c is pixel (c / 64) * 64 * Wn + 64 * w + c % 64
     const long long w = (long long)blockIdx.x * kWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -144,7 +107,7 @@ __global__ __launch_bounds__(kThreads) void k_trace_camera(CamArgs a) {
     }
 }
 
-// load_camera's premise: the kernel's one parameter is CamArgs, at offset 0 of the argument segment.
+// ptb::load_arg's premise: the kernel's one parameter is CamArgs, at offset 0 of the argument segment.
 static_assert(std::is_same<decltype(&k_trace_camera<-1>), void (*)(CamArgs)>::value, "CamArgs is the only kernel parameter");
 
 // One thread per pixel: the ray of frame `frame` as two quads, and the state the camera left.
@@ -158,20 +121,6 @@ __global__ __launch_bounds__(kThreads) void k_camera_rays(Prepared cam, int fram
     rays[2 * i] = make_float4(o.x, o.y, o.z, __builtin_huge_valf());
     rays[2 * i + 1] = make_float4(d.x, d.y, d.z, 0.0f);
     if (states) states[i] = state;
-}
-
-// Workgroups of kernel `fn` that a device holds at once: compute units x workgroups per unit at its occupancy.
-// Asked of the runtime once per kernel and device.
-int resident_blocks(const void* fn, int which, int device) {
-    static int cache[kKernels][kMaxDevices];
-    if (device < 0 || device >= kMaxDevices) return 1024;
-    if (cache[which][device] == 0) {
-        int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kThreads, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 1) cus = 256;
-        cache[which][device] = per_cu * cus;
-    }
-    return cache[which][device];
 }
 
 }  // namespace
@@ -190,11 +139,9 @@ hipError_t launch_trace_camera(hipStream_t s, const ptt::CtxView& v, const Launc
            : l.cam.model == PT_CAM_THIN_LENS ? k_trace_camera<PT_CAM_THIN_LENS>
            : l.cam.model == PT_CAM_ORTHO ? k_trace_camera<PT_CAM_ORTHO> : k_trace_camera<PT_CAM_EQUIRECT>;
     }
-    long long blocks = resident_blocks((const void*)fn, which, v.q.device);
-    const long long want = (n + kThreads - 1) / kThreads;
-    if (want < blocks) blocks = want;
-    if (l.grid_cap > 0 && l.grid_cap < blocks) blocks = l.grid_cap;
-    hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(kThreads), 0, s, a);
+    static ptb::Resident resident[kKernels];
+    const unsigned blocks = ptb::persistent_grid((const void*)fn, resident[which], v.q.device, n, l.grid_cap);
+    hipLaunchKernelGGL(fn, dim3(blocks), dim3(kThreads), 0, s, a);
     return hipGetLastError();
 }
 
@@ -213,33 +160,15 @@ namespace {
 
 int g_grid_cap = 0, g_per_model = 0;       // pt__camera_debug (measurements and tests only)
 
-int hip_fail(pt_ctx* c, const char* what, hipError_t e) {
-    return pt__query_fail(c, PT_E_HIP, (std::string(what) + ": " + hipGetErrorString(e)).c_str());
-}
-#define CCHK(ctx, call)                                       \
-    do {                                                      \
-        hipError_t e_ = (call);                               \
-        if (e_ != hipSuccess) return hip_fail(ctx, #call, e_); \
-    } while (0)
-
-int check_camera(pt_ctx* c, const pt_camera* cam) {
-    if (ptcam::validate(cam) != PT_OK)
-        return pt__query_fail(c, PT_E_ARG, "camera: null, unknown model or flag, size out of range, or a bad aperture, "
-                                           "focus or ortho_width for its model");
-    return PT_OK;
-}
-
 // the checks both trace entry points share
 int check_trace(pt_ctx* c, const pt_camera* cam, int frame_first, int n_frames, int accumulate_first, const void* rgba,
                 const char* who, ptt::CtxView& v) {
     if (!c) return PT_E_ARG;
     int rc = pt__trace_view(c, &v);
     if (rc) return rc;
-    if (!v.q.scene_ok) return pt__query_fail(c, PT_E_STATE, (std::string(who) + " before pt_upload_scene").c_str());
-    if ((rc = check_camera(c, cam)) != PT_OK) return rc;
-    if (frame_first < 1 || n_frames < 1) return pt__query_fail(c, PT_E_ARG, "frame_first and n_frames must be >= 1");
-    if (frame_first > INT_MAX - n_frames) return pt__query_fail(c, PT_E_ARG, "frame_first + n_frames overflows");
-    if (accumulate_first != 0 && accumulate_first != 1) return pt__query_fail(c, PT_E_ARG, "accumulate_first must be 0 or 1");
+    if ((rc = pte::check_scene(c, v.q, who)) != PT_OK) return rc;
+    if ((rc = pte::check_camera(c, cam)) != PT_OK) return rc;
+    if ((rc = pte::check_frames(c, frame_first, n_frames, accumulate_first)) != PT_OK) return rc;
     if (!rgba) return pt__query_fail(c, PT_E_ARG, "null rgba");
     return PT_OK;
 }
@@ -248,7 +177,7 @@ int enqueue(pt_ctx* c, const ptt::CtxView& v, const pt_camera* cam, int frame_fi
             void* d_rgba) {
     const ptcam::Launch l = {ptcam::prepare(*cam), (float4*)d_rgba, frame_first, n_frames, accumulate_first, g_grid_cap,
                              g_per_model == 1};
-    CCHK(c, ptcam::launch_trace_camera(v.q.stream, v, l));
+    PTCHK(c, ptcam::launch_trace_camera(v.q.stream, v, l));
     return PT_OK;
 }
 
@@ -262,7 +191,7 @@ int pt_trace_camera_device(pt_ctx* c, const pt_camera* cam, int frame_first, int
     const int rc = check_trace(c, cam, frame_first, n_frames, accumulate_first, d_rgba, "pt_trace_camera_device", v);
     if (rc) return rc;
     if ((size_t)d_rgba & 15u) return pt__query_fail(c, PT_E_ARG, "device rgba must be 16-byte aligned");
-    CCHK(c, hipSetDevice(v.q.device));
+    PTCHK(c, hipSetDevice(v.q.device));
     return enqueue(c, v, cam, frame_first, n_frames, accumulate_first, d_rgba);
 }
 
@@ -270,23 +199,15 @@ int pt_trace_camera(pt_ctx* c, const pt_camera* cam, int frame_first, int n_fram
     ptt::CtxView v;
     int rc = check_trace(c, cam, frame_first, n_frames, accumulate_first, rgba, "pt_trace_camera", v);
     if (rc) return rc;
-    CCHK(c, hipSetDevice(v.q.device));
+    PTCHK(c, hipSetDevice(v.q.device));
     const size_t rgba_bytes = (size_t)cam->width * (size_t)cam->height * 4 * sizeof(float);
-    void* d_rgba = nullptr;
-    hipError_t e = hipMalloc(&d_rgba, rgba_bytes);
+    pte::Staged b(v.q.stream);
+    void* d_rgba = b.alloc(rgba_bytes);
     // the caller's values are the prior of an accumulating first frame; otherwise rgba is never read
-    if (e == hipSuccess && accumulate_first) e = hipMemcpyAsync(d_rgba, rgba, rgba_bytes, hipMemcpyHostToDevice, v.q.stream);
-    if (e == hipSuccess) {
-        rc = enqueue(c, v, cam, frame_first, n_frames, accumulate_first, d_rgba);
-        if (rc == PT_OK) {
-            e = hipMemcpyAsync(rgba, d_rgba, rgba_bytes, hipMemcpyDeviceToHost, v.q.stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(v.q.stream);
-        }
-    }
-    if (e != hipSuccess) (void)hipStreamSynchronize(v.q.stream);   // nothing in flight may still read the buffer
-    (void)hipFree(d_rgba);
-    if (e != hipSuccess) return hip_fail(c, "pt_trace_camera", e);
-    return rc;
+    if (accumulate_first) b.in(d_rgba, rgba, rgba_bytes);
+    if (b.ok() && (rc = enqueue(c, v, cam, frame_first, n_frames, accumulate_first, d_rgba)) == PT_OK)
+        b.out(rgba, d_rgba, rgba_bytes);
+    return b.ok() ? rc : pte::hip_fail(c, "pt_trace_camera", b.e);
 }
 
 int pt_camera_rays_device(pt_ctx* c, const pt_camera* cam, int frame, void* d_rays, void* d_states) {
@@ -294,12 +215,12 @@ int pt_camera_rays_device(pt_ctx* c, const pt_camera* cam, int frame, void* d_ra
     ptt::CtxView v;
     int rc = pt__trace_view(c, &v);
     if (rc) return rc;
-    if ((rc = check_camera(c, cam)) != PT_OK) return rc;
+    if ((rc = pte::check_camera(c, cam)) != PT_OK) return rc;
     if (frame < 1) return pt__query_fail(c, PT_E_ARG, "frame must be >= 1");
     if (!d_rays || ((size_t)d_rays & 15u) || ((size_t)d_states & 3u))
         return pt__query_fail(c, PT_E_ARG, "device rays must be non-null and 16-byte aligned, states 4-byte aligned");
-    CCHK(c, hipSetDevice(v.q.device));
-    CCHK(c, ptcam::launch_camera_rays(v.q.stream, ptcam::prepare(*cam), frame, (float4*)d_rays, (unsigned*)d_states));
+    PTCHK(c, hipSetDevice(v.q.device));
+    PTCHK(c, ptcam::launch_camera_rays(v.q.stream, ptcam::prepare(*cam), frame, (float4*)d_rays, (unsigned*)d_states));
     return PT_OK;
 }
 

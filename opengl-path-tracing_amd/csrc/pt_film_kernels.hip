@@ -12,25 +12,30 @@
 // them with the pixel, MREG = false reads and writes the pixel's 8 bytes at each path end (DESIGN.md §15.4 has the
 // measurement that chose).  What only those places read -- the three plane pointers, the guide range, the guides-only
 // flag -- is read back from the argument segment there, like the camera.
-// TWIN: k_trace_camera<-1> (pt_camera_kernels.hip), the refill loop.
+// TWIN: k_trace_camera<-1> (pt_camera_kernels.hip), the refill loop (one shared loop moved the
+// registers of all three kernels).
+// Shared with the other ray-batch units: the scene accessor, rank_in, the argument-segment read, the
+// compute-unit count and the persistent grid's size come from pt_batch_device.h, the error return and the checks of the
+// entry points from pt_entry.h.
 #include "pt_film_launch.h"
 
+#include "pt_batch_device.h"
 #include "pt_denoise_launch.h"
+#include "pt_entry.h"
 #include "pt_scene_pack.h"
 
 #include <climits>
 #include <cstddef>
 #include <cstring>
-#include <string>
 #include <type_traits>
 #include <vector>
 
 namespace ptfilm {
 namespace {
 
-constexpr int kThreads = 256;              // a workgroup: 4 waves
-constexpr int kWaves = kThreads / 64;
-constexpr int kMaxDevices = 64;
+using ptb::kThreads;
+using ptb::kWaves;
+using ptb::rank_in;
 
 // What the guide fold and the path end read, and nothing else does.
 struct Rare {
@@ -55,46 +60,9 @@ struct FilmArgs {
     ptcam::Prepared cam;
 };
 
-// TWIN: DevScene (pt_camera_kernels.hip).
-struct DevScene {
-    const FilmArgs& a;
-    __device__ __forceinline__ int n_nodes() const { return a.n_nodes; }
-    __device__ __forceinline__ int n_spheres() const { return a.n_spheres; }
-    __device__ __forceinline__ bool scene_fast() const { return a.scene_fast != 0; }
-    __device__ __forceinline__ void node(int i, float4& lo, float4& hi) const {
-        lo = a.nodes[2 * (size_t)i];
-        hi = a.nodes[2 * (size_t)i + 1];
-    }
-    __device__ __forceinline__ float4 tri(int slot, int k) const { return a.tris[4 * (size_t)slot + k]; }
-    __device__ __forceinline__ float4 sphere(int i, int k) const { return a.spheres[2 * (size_t)i + k]; }
-    __device__ __forceinline__ float4 leaf_tris(int pair) const { return a.leaf_tris[pair]; }
-    __device__ __forceinline__ float4 mat(int i, int k) const { return a.mats[3 * (size_t)i + k]; }
-};
-
-// Number of set bits of m below this lane.
-__device__ __forceinline__ int rank_in(unsigned long long m) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
-
-// A member of FilmArgs read from the kernel's argument segment where it is used, by vector loads (every lane the same
-// words): nothing of it is live during the walk.  pt_camera_kernels.hip's load_camera() has the measurement behind
-// the device -- as by-value arguments these words stay in SGPRs across the whole loop and cost a wave per SIMD
-//  -- and what it relies on: FilmArgs is the kernel's first and only parameter, so that it starts
-// the argument segment (asserted below the kernel).  The empty asm makes the address opaque and per-lane, so the
-// loads are neither hoisted out of the loop nor turned back into scalar ones.
-template <class T, size_t OFFSET>
-__device__ __forceinline__ T load_arg() {
-    typedef const __attribute__((address_space(4))) uint32_t* kernarg_words;
-    static_assert(OFFSET % 4 == 0 && sizeof(T) % 4 == 0, "whole words");
-    kernarg_words w = (kernarg_words)__builtin_amdgcn_kernarg_segment_ptr() + OFFSET / 4;
-    asm volatile("" : "+v"(w));
-    union { T t; uint32_t u[sizeof(T) / 4]; } c;
-#pragma unroll
-    for (int k = 0; k < (int)(sizeof(T) / 4); k++) c.u[k] = w[k];
-    return c.t;
-}
-__device__ __forceinline__ ptcam::Prepared load_camera() { return load_arg<ptcam::Prepared, offsetof(FilmArgs, cam)>(); }
-__device__ __forceinline__ Rare load_rare() { return load_arg<Rare, offsetof(FilmArgs, rare)>(); }
+// The camera and the rare words, read back from the argument segment where they are used (ptb::load_arg has the why).
+__device__ __forceinline__ ptcam::Prepared load_camera() { return ptb::load_arg<ptcam::Prepared, offsetof(FilmArgs, cam)>(); }
+__device__ __forceinline__ Rare load_rare() { return ptb::load_arg<Rare, offsetof(FilmArgs, rare)>(); }
 
 // amdgpu_num_sgpr(96): left alone the compiler keeps literal constants of the walk in scalar registers for as long as
 // there are any, 98 in all, and beyond 96 a SIMD holds 6 of this kernel's waves although the occupancy query says 7, so
@@ -102,7 +70,7 @@ __device__ __forceinline__ Rare load_rare() { return load_arg<Rare, offsetof(Fil
 // exposure was 32-37% slower than the plain camera trace on both scenes, and 1-3% with the cap.
 template <bool MREG>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_num_sgpr(96))) void k_film_expose(FilmArgs a) {
-    const DevScene sc = {a};
+    const ptb::DevScene<FilmArgs> sc = {a};
     const ptt::Frames fr = a.fr;
     // the wave's share: cursor position c is pixel (c / 64) * 64 * Wn + 64 * w + c % 64
     const long long w = (long long)blockIdx.x * kWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -196,7 +164,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_num_sgpr(96))) void
     }
 }
 
-// load_arg's premise: the kernel's one parameter is FilmArgs, at offset 0 of the argument segment.
+// ptb::load_arg's premise: the kernel's one parameter is FilmArgs, at offset 0 of the argument segment.
 static_assert(std::is_same<decltype(&k_film_expose<false>), void (*)(FilmArgs)>::value, "FilmArgs is the only kernel parameter");
 static_assert(std::is_same<decltype(&k_film_expose<true>), void (*)(FilmArgs)>::value, "FilmArgs is the only kernel parameter");
 
@@ -264,29 +232,6 @@ __global__ __launch_bounds__(kThreads) void k_film_aces(const float4* __restrict
     if (i < n) dst[i] = pti::aces_px<uchar4>(src[i]);
 }
 
-int compute_units(int device) {
-    static int cache[kMaxDevices];
-    if (device < 0 || device >= kMaxDevices) return 256;
-    if (cache[device] == 0) {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 1) cus = 256;
-        cache[device] = cus;
-    }
-    return cache[device];
-}
-
-// Workgroups of kernel `fn` that a device holds at once (as pt_camera_kernels.hip's): asked once per kernel and device.
-int resident_blocks(const void* fn, int which, int device) {
-    static int cache[2][kMaxDevices];
-    if (device < 0 || device >= kMaxDevices) return 1024;
-    if (cache[which][device] == 0) {
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kThreads, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-        cache[which][device] = per_cu * compute_units(device);
-    }
-    return cache[which][device];
-}
-
 }  // namespace
 
 hipError_t launch_expose(hipStream_t s, const ptt::CtxView& v, const Launch& l) {
@@ -297,11 +242,10 @@ hipError_t launch_expose(hipStream_t s, const ptt::CtxView& v, const Launch& l) 
     const FilmArgs a = {v.q.nodes, v.q.tris, v.q.spheres, v.q.leaf_tris, v.mats, l.rgba, n,
                         v.q.n_nodes, v.q.n_spheres, v.q.scene_fast, fr, rare, l.cam};
     void (*fn)(FilmArgs) = l.moments_in_regs ? k_film_expose<true> : k_film_expose<false>;
-    long long blocks = resident_blocks((const void*)fn, l.moments_in_regs ? 1 : 0, v.q.device);
-    const long long want = (n + kThreads - 1) / kThreads;
-    if (want < blocks) blocks = want;
-    if (l.grid_cap > 0 && l.grid_cap < blocks) blocks = l.grid_cap;
-    hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(kThreads), 0, s, a);
+    static ptb::Resident resident[2];
+    const unsigned blocks = ptb::persistent_grid((const void*)fn, resident[l.moments_in_regs ? 1 : 0], v.q.device, n,
+                                                 l.grid_cap);
+    hipLaunchKernelGGL(fn, dim3(blocks), dim3(kThreads), 0, s, a);
     return hipGetLastError();
 }
 
@@ -309,7 +253,7 @@ hipError_t launch_noise(hipStream_t s, int device, const float2* moments, long l
                         pt_noise_stats* out) {
     if (n <= 0) return hipSuccess;
     long long blocks = (n + kThreads - 1) / kThreads;
-    const long long cap = 2LL * compute_units(device);      // k_noise's grid: two blocks per compute unit
+    const long long cap = 2LL * ptb::compute_units(device);      // k_noise's grid: two blocks per compute unit
     if (blocks > cap) blocks = cap;
     hipLaunchKernelGGL(k_film_noise, dim3((unsigned)blocks), dim3(kThreads), 0, s, moments, (unsigned long long)n, frames,
                        target_q, out);
@@ -351,15 +295,6 @@ namespace {
 int g_grid_cap = 0, g_moments = 0;         // pt__film_debug (measurements and tests only)
 constexpr bool kMomentsInRegs = false;     // what ships
 
-int hip_fail(pt_ctx* c, const char* what, hipError_t e) {
-    return pt__query_fail(c, PT_E_HIP, (std::string(what) + ": " + hipGetErrorString(e)).c_str());
-}
-#define FCHK(ctx, call)                                       \
-    do {                                                      \
-        hipError_t e_ = (call);                               \
-        if (e_ != hipSuccess) return hip_fail(ctx, #call, e_); \
-    } while (0)
-
 void free_film(pt_film* f) {
     (void)hipFree(f->image), (void)hipFree(f->moments), (void)hipFree(f->guide), (void)hipFree(f->state[0]);
     (void)hipFree(f->state[1]), (void)hipFree(f->denoised), (void)hipFree(f->rgba8), (void)hipFree(f->d_noise);
@@ -375,14 +310,7 @@ int enter(pt_film* f, ptt::CtxView& v) {
     unsigned long long serial = 0;
     if ((rc = pt__scene_serial(f->ctx, &serial)) != PT_OK) return rc;
     if (serial != f->serial) f->serial = serial, f->guides_held = 0;
-    FCHK(f->ctx, hipSetDevice(v.q.device));
-    return PT_OK;
-}
-
-int check_frames(pt_ctx* c, int frame_first, int n_frames, int accumulate_first) {
-    if (frame_first < 1 || n_frames < 1) return pt__query_fail(c, PT_E_ARG, "frame_first and n_frames must be >= 1");
-    if (frame_first > INT_MAX - n_frames) return pt__query_fail(c, PT_E_ARG, "frame_first + n_frames overflows");
-    if (accumulate_first != 0 && accumulate_first != 1) return pt__query_fail(c, PT_E_ARG, "accumulate_first must be 0 or 1");
+    PTCHK(f->ctx, hipSetDevice(v.q.device));
     return PT_OK;
 }
 
@@ -402,7 +330,7 @@ int expose(pt_film* f, const ptt::CtxView& v, int frame_first, int n_frames, int
     ptfilm::Launch l = launch_of(f);
     l.frame_first = frame_first, l.n_frames = n_frames, l.acc_first = accumulate_first;
     l.guides = ptfilm::guide_range(frame_first, n_frames, f->guides_held, f->guide_frames);
-    FCHK(f->ctx, ptfilm::launch_expose(v.q.stream, v, l));
+    PTCHK(f->ctx, ptfilm::launch_expose(v.q.stream, v, l));
     f->guides_held = ptfilm::held_after(l.guides, f->guides_held);
     // (a count past INT_MAX stays there: the noise estimate's n is an int)
     f->frames = accumulate_first ? (f->frames > INT_MAX - n_frames ? INT_MAX : f->frames + n_frames) : n_frames;
@@ -410,10 +338,10 @@ int expose(pt_film* f, const ptt::CtxView& v, int frame_first, int n_frames, int
 }
 
 int noise(pt_film* f, const ptt::CtxView& v, float target, pt_noise_stats* out) {
-    FCHK(f->ctx, hipMemsetAsync(f->d_noise, 0, sizeof(pt_noise_stats), v.q.stream));
-    FCHK(f->ctx, ptfilm::launch_noise(v.q.stream, v.q.device, f->moments, f->px, f->frames, ptn::target_q(target), f->d_noise));
-    FCHK(f->ctx, hipMemcpyAsync(f->h_noise, f->d_noise, sizeof(pt_noise_stats), hipMemcpyDeviceToHost, v.q.stream));
-    FCHK(f->ctx, hipStreamSynchronize(v.q.stream));
+    PTCHK(f->ctx, hipMemsetAsync(f->d_noise, 0, sizeof(pt_noise_stats), v.q.stream));
+    PTCHK(f->ctx, ptfilm::launch_noise(v.q.stream, v.q.device, f->moments, f->px, f->frames, ptn::target_q(target), f->d_noise));
+    PTCHK(f->ctx, hipMemcpyAsync(f->h_noise, f->d_noise, sizeof(pt_noise_stats), hipMemcpyDeviceToHost, v.q.stream));
+    PTCHK(f->ctx, hipStreamSynchronize(v.q.stream));
     *out = *f->h_noise;
     out->frames = f->frames;
     return PT_OK;
@@ -429,13 +357,11 @@ int pt_film_create(pt_ctx* c, const pt_camera* cam, int guide_frames, pt_film** 
     ptt::CtxView v;
     int rc = pt__trace_view(c, &v);
     if (rc) return rc;
-    if (ptcam::validate(cam) != PT_OK)
-        return pt__query_fail(c, PT_E_ARG, "camera: null, unknown model or flag, size out of range, or a bad aperture, "
-                                           "focus or ortho_width for its model");
+    if ((rc = pte::check_camera(c, cam)) != PT_OK) return rc;
     if (guide_frames < 1) return pt__query_fail(c, PT_E_ARG, "pt_film_create: guide_frames must be >= 1");
     const long long px = (long long)cam->width * cam->height;
     if (px >= (1LL << 31)) return pt__query_fail(c, PT_E_ARG, "pt_film_create: width * height must be below 2^31");
-    FCHK(c, hipSetDevice(v.q.device));
+    PTCHK(c, hipSetDevice(v.q.device));
     pt_film* f = new pt_film;
     f->ctx = c, f->cam = *cam, f->px = px, f->guide_frames = guide_frames;
     (void)pt__scene_serial(c, &f->serial);
@@ -456,7 +382,7 @@ int pt_film_create(pt_ctx* c, const pt_camera* cam, int guide_frames, pt_film** 
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(v.q.stream);
         free_film(f);
-        return hip_fail(c, "pt_film_create", e);
+        return pte::hip_fail(c, "pt_film_create", e);
     }
     *out = f;
     return PT_OK;
@@ -472,9 +398,8 @@ void pt_film_destroy(pt_film* f) {
 
 int pt_film_set_camera(pt_film* f, const pt_camera* cam) {
     if (!f) return PT_E_ARG;
-    if (ptcam::validate(cam) != PT_OK)
-        return pt__query_fail(f->ctx, PT_E_ARG, "camera: null, unknown model or flag, size out of range, or a bad aperture, "
-                                                "focus or ortho_width for its model");
+    const int rc = pte::check_camera(f->ctx, cam);
+    if (rc) return rc;
     if (cam->width != f->cam.width || cam->height != f->cam.height)
         return pt__query_fail(f->ctx, PT_E_ARG, "pt_film_set_camera: the film keeps its size");
     f->cam = *cam;
@@ -486,8 +411,8 @@ int pt_film_expose(pt_film* f, int frame_first, int n_frames, int accumulate_fir
     ptt::CtxView v;
     int rc = enter(f, v);
     if (rc) return rc;
-    if (!v.q.scene_ok) return pt__query_fail(f->ctx, PT_E_STATE, "pt_film_expose before pt_upload_scene");
-    if ((rc = check_frames(f->ctx, frame_first, n_frames, accumulate_first)) != PT_OK) return rc;
+    if ((rc = pte::check_scene(f->ctx, v.q, "pt_film_expose")) != PT_OK) return rc;
+    if ((rc = pte::check_frames(f->ctx, frame_first, n_frames, accumulate_first)) != PT_OK) return rc;
     return expose(f, v, frame_first, n_frames, accumulate_first);
 }
 
@@ -509,8 +434,8 @@ int pt_film_expose_until(pt_film* f, int frame_first, int accumulate_first, int 
     if (rc) return rc;
     if (batch < 2 || max_frames < batch || !(target > 0.0f))
         return pt__query_fail(f->ctx, PT_E_ARG, "pt_film_expose_until: batch >= 2, max_frames >= batch, target > 0");
-    if (!v.q.scene_ok) return pt__query_fail(f->ctx, PT_E_STATE, "pt_film_expose_until before pt_upload_scene");
-    if ((rc = check_frames(f->ctx, frame_first, max_frames, accumulate_first)) != PT_OK) return rc;
+    if ((rc = pte::check_scene(f->ctx, v.q, "pt_film_expose_until")) != PT_OK) return rc;
+    if ((rc = pte::check_frames(f->ctx, frame_first, max_frames, accumulate_first)) != PT_OK) return rc;
     // TWIN: pt_render_until (pt_ctx_noise.h), the stop rule.
     const unsigned long long tq = ptn::target_q(target);
     pt_noise_stats s = {0, 0, 0, 0, 0};
@@ -537,7 +462,7 @@ int pt_film_denoise(pt_film* f, const pt_denoise_params* params, pt_denoise_info
     if (params) dp = *params;
     if (dp.iterations < 1 || dp.iterations > ptd::kMaxIterations) return pt__query_fail(c, PT_E_ARG, "pt_film_denoise: iterations must be 1..8");
     if (dp.guide_frames < 1) return pt__query_fail(c, PT_E_ARG, "pt_film_denoise: guide_frames must be >= 1");
-    if (!v.q.scene_ok) return pt__query_fail(c, PT_E_STATE, "pt_film_denoise before pt_upload_scene");
+    if ((rc = pte::check_scene(c, v.q, "pt_film_denoise")) != PT_OK) return rc;
     if (dp.guide_frames != f->guide_frames) f->guide_frames = dp.guide_frames, f->guides_held = 0;
     const bool gather = f->guides_held < f->guide_frames;
     if (gather) {                                  // the missing guide frames: first segments only
@@ -545,7 +470,7 @@ int pt_film_denoise(pt_film* f, const pt_denoise_params* params, pt_denoise_info
         l.frame_first = f->guides_held + 1, l.n_frames = f->guide_frames - f->guides_held;
         l.guides = {l.frame_first, f->guide_frames};
         l.guides_only = true;
-        FCHK(c, ptfilm::launch_expose(v.q.stream, v, l));
+        PTCHK(c, ptfilm::launch_expose(v.q.stream, v, l));
         f->guides_held = f->guide_frames;
     }
     const bool guided = f->frames >= 2;
@@ -558,7 +483,7 @@ int pt_film_denoise(pt_film* f, const pt_denoise_params* params, pt_denoise_info
         ptd::launch_iter(v.q.stream, im, f->state[i & 1], last ? f->denoised : f->state[(i + 1) & 1], f->guide,
                          f->guide + f->px, last ? f->image : nullptr, 1 << i, guided, k, ptd::kAuto);
     }
-    FCHK(c, hipGetLastError());
+    PTCHK(c, hipGetLastError());
     f->dn_done = true;
     if (info) *info = {guided ? 1 : 0, gather ? 1 : 0, dp.iterations, f->frames};
     return PT_OK;
@@ -601,17 +526,17 @@ int pt_film_read(pt_film* f, int what, void* dst, size_t bytes) {
     const void* src = what == PT_FILM_IMAGE ? (const void*)f->image : what == PT_FILM_MOMENTS ? (const void*)f->moments
                     : what == PT_FILM_DENOISED ? (const void*)f->denoised : (const void*)f->rgba8;
     if (what == PT_FILM_IMAGE_ACES8 || what == PT_FILM_DENOISED_ACES8)
-        FCHK(c, ptfilm::launch_aces(v.q.stream, what == PT_FILM_IMAGE_ACES8 ? f->image : f->denoised, f->rgba8, f->px));
-    FCHK(c, hipStreamSynchronize(v.q.stream));
+        PTCHK(c, ptfilm::launch_aces(v.q.stream, what == PT_FILM_IMAGE_ACES8 ? f->image : f->denoised, f->rgba8, f->px));
+    PTCHK(c, hipStreamSynchronize(v.q.stream));
     if (what != PT_FILM_GUIDES) {
-        FCHK(c, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+        PTCHK(c, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
         return PT_OK;
     }
     // the two planes interleaved per pixel: pt_read_guides' order
     std::vector<float> g(px * 4);
     float* out = (float*)dst;
     for (int h = 0; h < 2; h++) {
-        FCHK(c, hipMemcpy(g.data(), f->guide + (size_t)h * px, px * sizeof(float4), hipMemcpyDeviceToHost));
+        PTCHK(c, hipMemcpy(g.data(), f->guide + (size_t)h * px, px * sizeof(float4), hipMemcpyDeviceToHost));
         for (size_t i = 0; i < px; i++) std::memcpy(out + 8 * i + 4 * h, g.data() + 4 * i, 4 * sizeof(float));
     }
     return PT_OK;

@@ -2,34 +2,13 @@
 // the scene goes through ptp::pack_scene as an upload's does, and every ray runs ptq::cast (pt_query.h), the per-ray
 // code the device kernel runs, on the packed buffers.  The CPU suite (tests/test_query_host.py) checks it against a
 // numpy restatement of the reference bit for bit, and the GPU suite checks pt_intersect against this.
+// The scene accessor over the packed buffers and the settings checks are pt_host_scene.h's, shared by the four twins.
 #include "pt_query.h"
 
-#include "pt_scene_pack.h"
+#include "pt_host_scene.h"
 
 #include <cstring>
 #include <string>
-
-namespace {
-
-struct HostScene {
-    const ptp::Quad* nodes;
-    const ptp::Quad* tris;
-    const ptp::Quad* spheres;
-    const ptp::Quad* leaf;
-    int nn, ns;
-    bool fast;
-    int n_nodes() const { return nn; }
-    int n_spheres() const { return ns; }
-    bool scene_fast() const { return fast; }
-    void node(int i, ptp::Quad& lo, ptp::Quad& hi) const { lo = nodes[2 * (size_t)i], hi = nodes[2 * (size_t)i + 1]; }
-    ptp::Quad tri(int slot, int k) const { return tris[4 * (size_t)slot + k]; }
-    ptp::Quad sphere(int i, int k) const { return spheres[2 * (size_t)i + k]; }
-    ptp::Quad leaf_tris(int pair) const { return leaf[pair]; }
-};
-
-const ptp::Quad* quads_of(const ptp::PackedScene& p, int b) { return reinterpret_cast<const ptp::Quad*>(p.buf[b].data()); }
-
-}  // namespace
 
 extern "C" {
 
@@ -51,9 +30,7 @@ int pt_intersect_host(const float* tris, int n_tris, const float* bvh, int n_nod
     std::string err;
     const int rc = ptp::pack_scene(tris, n_tris, bvh, n_nodes, mats, n_mats, spheres, n_spheres, packed, err);
     if (rc) return rc;
-    const HostScene sc = {quads_of(packed, ptp::kNodes), quads_of(packed, ptp::kTris), quads_of(packed, ptp::kSpheres),
-                          quads_of(packed, ptp::kLeafTris), packed.facts.n_nodes, packed.facts.n_spheres,
-                          packed.facts.scene_fast != 0};
+    const pth::HostScene sc = pth::host_scene(packed);
     const bool any = (query_flags & PT_QUERY_ANY_HIT) != 0;
     for (long long i = 0; i < n; i++) {
         const pt_ray& r = rays[i];

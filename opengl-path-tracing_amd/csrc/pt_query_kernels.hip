@@ -7,17 +7,20 @@
 // exists for -- into LDS (at most 24 KiB, as two planes like the render's global-memory walk); a walk reads those from
 // LDS and the nodes beyond from global memory, one 16-byte load per quad.  The link choice is a select; the leaf's
 // triangle tests run under the exec mask of the lanes whose box test passed at a leaf.
+// Shared with the other ray-batch units: the scene accessor and the workgroup shape come from
+// pt_batch_device.h, the error return, the checks and the staged buffers of the entry points from pt_entry.h.
+#include "pt_batch_device.h"
+#include "pt_entry.h"
 #include "pt_query.h"
 #include "pt_query_launch.h"
 #include "pt_scene_pack.h"
 
-#include <string>
 #include <vector>
 
 namespace ptq {
 namespace {
 
-constexpr int kThreads = 256;          // a workgroup: 4 waves
+using ptb::kThreads;
 constexpr unsigned kMaxBlocks = 2048;  // 8 workgroups per CU of the 256; the loop strides over the rest
 
 struct CastArgs {
@@ -31,27 +34,6 @@ struct CastArgs {
     int n_nodes, n_spheres, n_top, scene_fast, flags;
 };
 
-template <bool STAGED>
-struct DevScene {
-    const CastArgs& a;
-    const float4* top;      // LDS: lo plane at [i], hi plane at [n_top + i]
-    __device__ __forceinline__ int n_nodes() const { return a.n_nodes; }
-    __device__ __forceinline__ int n_spheres() const { return a.n_spheres; }
-    __device__ __forceinline__ bool scene_fast() const { return a.scene_fast != 0; }
-    __device__ __forceinline__ void node(int i, float4& lo, float4& hi) const {
-        if (STAGED && i < a.n_top) {
-            lo = top[i];
-            hi = top[a.n_top + i];
-        } else {
-            lo = a.nodes[2 * (size_t)i];
-            hi = a.nodes[2 * (size_t)i + 1];
-        }
-    }
-    __device__ __forceinline__ float4 tri(int slot, int k) const { return a.tris[4 * (size_t)slot + k]; }
-    __device__ __forceinline__ float4 sphere(int i, int k) const { return a.spheres[2 * (size_t)i + k]; }
-    __device__ __forceinline__ float4 leaf_tris(int pair) const { return a.leaf_tris[pair]; }
-};
-
 template <bool ANY, bool STAGED>
 __global__ __launch_bounds__(kThreads) void k_cast(CastArgs a) {
     __shared__ float4 s_top[STAGED ? 2 * ptp::kTopNodes : 1];
@@ -62,7 +44,7 @@ __global__ __launch_bounds__(kThreads) void k_cast(CastArgs a) {
         }
         __syncthreads();
     }
-    const DevScene<STAGED> sc = {a, s_top};
+    const ptb::DevScene<CastArgs, STAGED> sc = {a, s_top};
     const long long stride = (long long)gridDim.x * kThreads;
     for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < a.n; i += stride) {
         const float4 r0 = a.rays[2 * i], r1 = a.rays[2 * i + 1];
@@ -100,22 +82,13 @@ namespace {
 
 int g_query_variant = ptq::kAuto;     // pt__query_debug (measurements only)
 
-int hip_fail(pt_ctx* c, const char* what, hipError_t e) {
-    return pt__query_fail(c, PT_E_HIP, (std::string(what) + ": " + hipGetErrorString(e)).c_str());
-}
-#define QCHK(ctx, call)                                       \
-    do {                                                      \
-        hipError_t e_ = (call);                               \
-        if (e_ != hipSuccess) return hip_fail(ctx, #call, e_); \
-    } while (0)
-
 // the checks every entry point shares; n = 0 is the caller's early PT_OK
 int check_query(pt_ctx* c, const void* in, long long n, const void* out, int query_flags, const char* who,
                 ptq::CtxView& v) {
     if (!c) return PT_E_ARG;
     int rc = pt__query_view(c, &v);
     if (rc) return rc;
-    if (!v.scene_ok) return pt__query_fail(c, PT_E_STATE, (std::string(who) + " before pt_upload_scene").c_str());
+    if ((rc = pte::check_scene(c, v, who)) != PT_OK) return rc;
     if (n < 0) return pt__query_fail(c, PT_E_ARG, "negative ray count");
     if (query_flags & ~PT_QUERY_ANY_HIT) return pt__query_fail(c, PT_E_ARG, "unknown query flags");
     if (n > 0 && (!in || !out)) return pt__query_fail(c, PT_E_ARG, "null array with a nonzero count");
@@ -125,7 +98,7 @@ int check_query(pt_ctx* c, const void* in, long long n, const void* out, int que
 int enqueue(pt_ctx* c, const ptq::CtxView& v, const void* d_rays, long long n, void* d_hits, int query_flags) {
     const bool staged = g_query_variant != ptq::kGlobal && v.kernel_variant != 3;
     const ptq::Launch l = {(const float4*)d_rays, (float4*)d_hits, n, (query_flags & PT_QUERY_ANY_HIT) != 0, staged};
-    QCHK(c, ptq::launch_cast(v.stream, v, l));
+    PTCHK(c, ptq::launch_cast(v.stream, v, l));
     return PT_OK;
 }
 
@@ -138,7 +111,7 @@ int pt_intersect_device(pt_ctx* c, const void* d_rays, long long n, void* d_hits
     const int rc = check_query(c, d_rays, n, d_hits, query_flags, "pt_intersect_device", v);
     if (rc || n == 0) return rc;
     if (((size_t)d_rays | (size_t)d_hits) & 15u) return pt__query_fail(c, PT_E_ARG, "device arrays must be 16-byte aligned");
-    QCHK(c, hipSetDevice(v.device));
+    PTCHK(c, hipSetDevice(v.device));
     return enqueue(c, v, d_rays, n, d_hits, query_flags);
 }
 
@@ -146,24 +119,14 @@ int pt_intersect(pt_ctx* c, const pt_ray* rays, long long n, pt_hit* hits, int q
     ptq::CtxView v;
     int rc = check_query(c, rays, n, hits, query_flags, "pt_intersect", v);
     if (rc || n == 0) return rc;
-    QCHK(c, hipSetDevice(v.device));
-    void* d_rays = nullptr;
-    void* d_hits = nullptr;
-    hipError_t e = hipMalloc(&d_rays, (size_t)n * sizeof(pt_ray));
-    if (e == hipSuccess) e = hipMalloc(&d_hits, (size_t)n * sizeof(pt_hit));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_rays, rays, (size_t)n * sizeof(pt_ray), hipMemcpyHostToDevice, v.stream);
-    if (e == hipSuccess) {
-        rc = enqueue(c, v, d_rays, n, d_hits, query_flags);
-        if (rc == PT_OK) {
-            e = hipMemcpyAsync(hits, d_hits, (size_t)n * sizeof(pt_hit), hipMemcpyDeviceToHost, v.stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(v.stream);
-        }
-    }
-    if (e != hipSuccess) (void)hipStreamSynchronize(v.stream);   // nothing in flight may still read the buffers
-    (void)hipFree(d_rays);
-    (void)hipFree(d_hits);
-    if (e != hipSuccess) return hip_fail(c, "pt_intersect", e);
-    return rc;
+    PTCHK(c, hipSetDevice(v.device));
+    pte::Staged b(v.stream);
+    void* d_rays = b.alloc((size_t)n * sizeof(pt_ray));
+    void* d_hits = b.alloc((size_t)n * sizeof(pt_hit));
+    b.in(d_rays, rays, (size_t)n * sizeof(pt_ray));
+    if (b.ok() && (rc = enqueue(c, v, d_rays, n, d_hits, query_flags)) == PT_OK)
+        b.out(hits, d_hits, (size_t)n * sizeof(pt_hit));
+    return b.ok() ? rc : pte::hip_fail(c, "pt_intersect", b.e);
 }
 
 int pt_pick(pt_ctx* c, const int* xy, long long n, pt_hit* hits) {

@@ -2,36 +2,12 @@
 // scene goes through ptp::pack_scene as an upload's does, and every ray runs ptt::trace_frames (pt_trace.h), the
 // per-ray code the device kernel runs, on the packed buffers.  The CPU suite (tests/test_trace_host.py) checks it
 // against the oracle's renders bit for bit, and the GPU suite checks pt_trace against this.
+// The scene accessor over the packed buffers and the settings checks are pt_host_scene.h's, shared by the four twins.
 #include "pt_trace.h"
 
-#include "pt_scene_pack.h"
+#include "pt_host_scene.h"
 
-#include <climits>
 #include <string>
-
-namespace {
-
-struct HostScene {
-    const ptp::Quad* nodes;
-    const ptp::Quad* tris;
-    const ptp::Quad* spheres;
-    const ptp::Quad* leaf;
-    const ptp::Quad* mats;
-    int nn, ns;
-    bool fast;
-    int n_nodes() const { return nn; }
-    int n_spheres() const { return ns; }
-    bool scene_fast() const { return fast; }
-    void node(int i, ptp::Quad& lo, ptp::Quad& hi) const { lo = nodes[2 * (size_t)i], hi = nodes[2 * (size_t)i + 1]; }
-    ptp::Quad tri(int slot, int k) const { return tris[4 * (size_t)slot + k]; }
-    ptp::Quad sphere(int i, int k) const { return spheres[2 * (size_t)i + k]; }
-    ptp::Quad leaf_tris(int pair) const { return leaf[pair]; }
-    ptp::Quad mat(int i, int k) const { return mats[3 * (size_t)i + k]; }
-};
-
-const ptp::Quad* quads_of(const ptp::PackedScene& p, int b) { return reinterpret_cast<const ptp::Quad*>(p.buf[b].data()); }
-
-}  // namespace
 
 extern "C" {
 
@@ -47,17 +23,14 @@ int pt__trace_host_segments(const float* tris, int n_tris, const float* bvh, int
                             const float* spheres, int n_spheres, int ctx_flags, int max_bounce, int display_mode,
                             const pt_ray* rays, const unsigned* seeds, long long n, int frame_first, int n_frames,
                             int accumulate_first, float* rgba, long long* segments) {
-    if (n < 0 || (ctx_flags & ~PT_FLAG_ALL) || max_bounce < 0 || display_mode < 1 || display_mode > 4) return PT_E_ARG;
-    if (frame_first < 1 || n_frames < 1 || frame_first > INT_MAX - n_frames) return PT_E_ARG;
-    if (accumulate_first != 0 && accumulate_first != 1) return PT_E_ARG;
+    if (n < 0 || !pth::settings_ok(ctx_flags, max_bounce, display_mode)) return PT_E_ARG;
+    if (!pth::frames_ok(frame_first, n_frames, accumulate_first)) return PT_E_ARG;
     if (n > 0 && (!rays || !rgba)) return PT_E_ARG;
     ptp::PackedScene packed;
     std::string err;
     const int rc = ptp::pack_scene(tris, n_tris, bvh, n_nodes, mats, n_mats, spheres, n_spheres, packed, err);
     if (rc) return rc;
-    const HostScene sc = {quads_of(packed, ptp::kNodes), quads_of(packed, ptp::kTris), quads_of(packed, ptp::kSpheres),
-                          quads_of(packed, ptp::kLeafTris), quads_of(packed, ptp::kMats), packed.facts.n_nodes,
-                          packed.facts.n_spheres, packed.facts.scene_fast != 0};
+    const pth::HostScene sc = pth::host_scene(packed);
     const ptt::Frames fr = {ctx_flags, max_bounce, display_mode, frame_first, n_frames, accumulate_first};
     for (long long i = 0; i < n; i++) {
         const pt_ray& r = rays[i];

@@ -15,19 +15,21 @@
 // ballot), then every live lane runs one segment; a lane whose path ended folds the colour into its running mean
 // (registers) and restarts the next frame from the ray, which it reloads.  Frames of a ray stay in order.
 // !REFILL: a plain grid-stride loop, one ray per lane to the end (ptt::trace_frames).
+// Shared with the other ray-batch units: the scene accessor, rank_in and the persistent grid's size
+// come from pt_batch_device.h, the error return, the checks and the staged buffers of the entry points from pt_entry.h.
+// The staging prologue and the refill loop are restated on purpose: §16.2.
+#include "pt_batch_device.h"
+#include "pt_entry.h"
 #include "pt_trace.h"
 #include "pt_trace_launch.h"
 #include "pt_scene_pack.h"
 
-#include <climits>
-#include <string>
-
 namespace ptt {
 namespace {
 
-constexpr int kThreads = 256;              // a workgroup: 4 waves
-constexpr int kWaves = kThreads / 64;
-constexpr int kMaxDevices = 64;
+using ptb::kThreads;
+using ptb::kWaves;
+using ptb::rank_in;
 
 struct TraceArgs {
     const float4* nodes;
@@ -43,33 +45,6 @@ struct TraceArgs {
     Frames fr;
 };
 
-template <bool STAGED>
-struct DevScene {
-    const TraceArgs& a;
-    const float4* top;      // LDS: lo plane at [i], hi plane at [n_top + i]
-    __device__ __forceinline__ int n_nodes() const { return a.n_nodes; }
-    __device__ __forceinline__ int n_spheres() const { return a.n_spheres; }
-    __device__ __forceinline__ bool scene_fast() const { return a.scene_fast != 0; }
-    __device__ __forceinline__ void node(int i, float4& lo, float4& hi) const {
-        if (STAGED && i < a.n_top) {
-            lo = top[i];
-            hi = top[a.n_top + i];
-        } else {
-            lo = a.nodes[2 * (size_t)i];
-            hi = a.nodes[2 * (size_t)i + 1];
-        }
-    }
-    __device__ __forceinline__ float4 tri(int slot, int k) const { return a.tris[4 * (size_t)slot + k]; }
-    __device__ __forceinline__ float4 sphere(int i, int k) const { return a.spheres[2 * (size_t)i + k]; }
-    __device__ __forceinline__ float4 leaf_tris(int pair) const { return a.leaf_tris[pair]; }
-    __device__ __forceinline__ float4 mat(int i, int k) const { return a.mats[3 * (size_t)i + k]; }
-};
-
-// Number of set bits of m below this lane.
-__device__ __forceinline__ int rank_in(unsigned long long m) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
-
 __device__ __forceinline__ uint32_t seed_of(const TraceArgs& a, long long i) {
     return a.seeds ? a.seeds[i] : default_seed(i);
 }
@@ -84,7 +59,7 @@ __global__ __launch_bounds__(kThreads) void k_trace(TraceArgs a) {
         }
         __syncthreads();
     }
-    const DevScene<STAGED> sc = {a, s_top};
+    const ptb::DevScene<TraceArgs, STAGED> sc = {a, s_top};
     const Frames fr = a.fr;
     if (!REFILL) {
         const long long stride = (long long)gridDim.x * kThreads;
@@ -96,7 +71,8 @@ __global__ __launch_bounds__(kThreads) void k_trace(TraceArgs a) {
         }
         return;
     }
-    // TWIN: k_trace_camera (pt_camera_kernels.hip) restates this refill loop with the ray made by the lane, not loaded.
+    // TWIN: k_trace_camera (pt_camera_kernels.hip) restates this refill loop with the ray made by the lane, not loaded
+    // (one shared loop moved the registers of all three kernels).
     // the wave's share: cursor position c is ray (c / 64) * 64 * Wn + 64 * w + c % 64
     const long long w = (long long)blockIdx.x * kWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const long long Wn = (long long)gridDim.x * kWaves;
@@ -154,20 +130,6 @@ __global__ __launch_bounds__(kThreads) void k_trace(TraceArgs a) {
     }
 }
 
-// Workgroups of kernel `fn` that a device holds at once: compute units x workgroups per unit at its occupancy.
-// Asked of the runtime once per kernel and device.
-int resident_blocks(const void* fn, int which, int device) {
-    static int cache[4][kMaxDevices];
-    if (device < 0 || device >= kMaxDevices) return 1024;
-    if (cache[which][device] == 0) {
-        int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kThreads, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 1) cus = 256;
-        cache[which][device] = per_cu * cus;
-    }
-    return cache[which][device];
-}
-
 }  // namespace
 
 hipError_t launch_trace(hipStream_t s, const CtxView& v, const Launch& l) {
@@ -179,11 +141,10 @@ hipError_t launch_trace(hipStream_t s, const CtxView& v, const Launch& l) {
     const bool staged = l.staged && n_top > 0;
     void (*fn)(TraceArgs) = staged ? (l.refill ? k_trace<true, true> : k_trace<true, false>)
                                    : (l.refill ? k_trace<false, true> : k_trace<false, false>);
-    long long blocks = resident_blocks((const void*)fn, (staged ? 2 : 0) + (l.refill ? 1 : 0), v.q.device);
-    const long long want = (l.n + kThreads - 1) / kThreads;
-    if (want < blocks) blocks = want;
-    if (l.grid_cap > 0 && l.grid_cap < blocks) blocks = l.grid_cap;
-    hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(kThreads), 0, s, a);
+    static ptb::Resident resident[4];
+    const unsigned blocks = ptb::persistent_grid((const void*)fn, resident[(staged ? 2 : 0) + (l.refill ? 1 : 0)],
+                                                 v.q.device, l.n, l.grid_cap);
+    hipLaunchKernelGGL(fn, dim3(blocks), dim3(kThreads), 0, s, a);
     return hipGetLastError();
 }
 
@@ -194,26 +155,15 @@ namespace {
 
 int g_staging = 0, g_refill = 0, g_grid_cap = 0;     // pt__trace_debug (measurements and tests only)
 
-int hip_fail(pt_ctx* c, const char* what, hipError_t e) {
-    return pt__query_fail(c, PT_E_HIP, (std::string(what) + ": " + hipGetErrorString(e)).c_str());
-}
-#define TCHK(ctx, call)                                       \
-    do {                                                      \
-        hipError_t e_ = (call);                               \
-        if (e_ != hipSuccess) return hip_fail(ctx, #call, e_); \
-    } while (0)
-
 // the checks both entry points share; n = 0 is the caller's early PT_OK
 int check_trace(pt_ctx* c, const void* rays, long long n, int frame_first, int n_frames, int accumulate_first,
                 const void* rgba, const char* who, ptt::CtxView& v) {
     if (!c) return PT_E_ARG;
-    const int rc = pt__trace_view(c, &v);
+    int rc = pt__trace_view(c, &v);
     if (rc) return rc;
-    if (!v.q.scene_ok) return pt__query_fail(c, PT_E_STATE, (std::string(who) + " before pt_upload_scene").c_str());
+    if ((rc = pte::check_scene(c, v.q, who)) != PT_OK) return rc;
     if (n < 0) return pt__query_fail(c, PT_E_ARG, "negative ray count");
-    if (frame_first < 1 || n_frames < 1) return pt__query_fail(c, PT_E_ARG, "frame_first and n_frames must be >= 1");
-    if (frame_first > INT_MAX - n_frames) return pt__query_fail(c, PT_E_ARG, "frame_first + n_frames overflows");
-    if (accumulate_first != 0 && accumulate_first != 1) return pt__query_fail(c, PT_E_ARG, "accumulate_first must be 0 or 1");
+    if ((rc = pte::check_frames(c, frame_first, n_frames, accumulate_first)) != PT_OK) return rc;
     if (n > 0 && (!rays || !rgba)) return pt__query_fail(c, PT_E_ARG, "null array with a nonzero count");
     return PT_OK;
 }
@@ -226,7 +176,7 @@ int enqueue(pt_ctx* c, const ptt::CtxView& v, const void* d_rays, const void* d_
     const bool refill = g_refill != 2;
     const ptt::Launch l = {(const float4*)d_rays, (const unsigned*)d_seeds, (float4*)d_rgba, n, frame_first, n_frames,
                            accumulate_first, staged, refill, g_grid_cap};
-    TCHK(c, ptt::launch_trace(v.q.stream, v, l));
+    PTCHK(c, ptt::launch_trace(v.q.stream, v, l));
     return PT_OK;
 }
 
@@ -241,7 +191,7 @@ int pt_trace_device(pt_ctx* c, const void* d_rays, const void* d_seeds, long lon
     if (rc || n == 0) return rc;
     if ((((size_t)d_rays | (size_t)d_rgba) & 15u) || ((size_t)d_seeds & 3u))
         return pt__query_fail(c, PT_E_ARG, "device rays and rgba must be 16-byte aligned, seeds 4-byte aligned");
-    TCHK(c, hipSetDevice(v.q.device));
+    PTCHK(c, hipSetDevice(v.q.device));
     return enqueue(c, v, d_rays, d_seeds, n, frame_first, n_frames, accumulate_first, d_rgba);
 }
 
@@ -250,32 +200,20 @@ int pt_trace(pt_ctx* c, const pt_ray* rays, const unsigned* seeds, long long n, 
     ptt::CtxView v;
     int rc = check_trace(c, rays, n, frame_first, n_frames, accumulate_first, rgba, "pt_trace", v);
     if (rc || n == 0) return rc;
-    TCHK(c, hipSetDevice(v.q.device));
+    PTCHK(c, hipSetDevice(v.q.device));
     const size_t ray_bytes = (size_t)n * sizeof(pt_ray), seed_bytes = (size_t)n * sizeof(unsigned);
     const size_t rgba_bytes = (size_t)n * 4 * sizeof(float);
-    void* d_rays = nullptr;
-    void* d_seeds = nullptr;
-    void* d_rgba = nullptr;
-    hipError_t e = hipMalloc(&d_rays, ray_bytes);
-    if (e == hipSuccess) e = hipMalloc(&d_rgba, rgba_bytes);
-    if (e == hipSuccess && seeds) e = hipMalloc(&d_seeds, seed_bytes);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_rays, rays, ray_bytes, hipMemcpyHostToDevice, v.q.stream);
-    if (e == hipSuccess && seeds) e = hipMemcpyAsync(d_seeds, seeds, seed_bytes, hipMemcpyHostToDevice, v.q.stream);
+    pte::Staged b(v.q.stream);
+    void* d_rays = b.alloc(ray_bytes);
+    void* d_rgba = b.alloc(rgba_bytes);
+    void* d_seeds = seeds ? b.alloc(seed_bytes) : nullptr;
+    b.in(d_rays, rays, ray_bytes);
+    if (seeds) b.in(d_seeds, seeds, seed_bytes);
     // the caller's values are the prior of an accumulating first frame; otherwise rgba is never read
-    if (e == hipSuccess && accumulate_first) e = hipMemcpyAsync(d_rgba, rgba, rgba_bytes, hipMemcpyHostToDevice, v.q.stream);
-    if (e == hipSuccess) {
-        rc = enqueue(c, v, d_rays, d_seeds, n, frame_first, n_frames, accumulate_first, d_rgba);
-        if (rc == PT_OK) {
-            e = hipMemcpyAsync(rgba, d_rgba, rgba_bytes, hipMemcpyDeviceToHost, v.q.stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(v.q.stream);
-        }
-    }
-    if (e != hipSuccess) (void)hipStreamSynchronize(v.q.stream);   // nothing in flight may still read the buffers
-    (void)hipFree(d_rays);
-    (void)hipFree(d_seeds);
-    (void)hipFree(d_rgba);
-    if (e != hipSuccess) return hip_fail(c, "pt_trace", e);
-    return rc;
+    if (accumulate_first) b.in(d_rgba, rgba, rgba_bytes);
+    if (b.ok() && (rc = enqueue(c, v, d_rays, d_seeds, n, frame_first, n_frames, accumulate_first, d_rgba)) == PT_OK)
+        b.out(rgba, d_rgba, rgba_bytes);
+    return b.ok() ? rc : pte::hip_fail(c, "pt_trace", b.e);
 }
 
 // Measurements and tests only (tools/trace_measure.py, tests/test_gpu_trace.py), not part of the public ABI: a
