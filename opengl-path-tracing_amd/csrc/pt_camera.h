@@ -6,7 +6,7 @@
 // make_ray runs on state = pt::seed(x, y, frame), takes the camera's draws from it in a fixed order and leaves it for
 // Trace, as the reference's main does for its jitter (computeShader.c:530-542):
 //   1. unless PT_CAM_NO_AA: ax = random01, ay = random01 (else both 0, nothing drawn);
-//   2. u = div_mk(x + ax, W, RN(1/W)) - 0.5, v likewise with H: camera_ray's expressions (pt_render_phase.h);
+//   2. u = pti::film_coord(x + ax, W, RN(1/W)), v likewise with H;
 //   3. the model's own draws: the thin lens takes u1, then u2; the others none.
 // Every operation is a pt_math.h one (no libm by name: host and device libm differ); sin t = cosf_pinned(|t - pi/2|)
 // with pi/2 = 0.5f * 3.1415926f, whose argument stays below 3 pi/2 for t in [0, 2 pi], inside cosf_pinned's domain.
@@ -30,7 +30,7 @@ struct Prepared {
     int model, W, H, flags;
     float fW, fH, rW, rH;      // (float)W, (float)H, RN(1/W), RN(1/H) by the host's IEEE division
     f3 pos, fwd, right;
-    f3 upS;                    // ptq::camera_basis's up: upU * H / W
+    f3 upS;                    // pti::camera_basis's up: upU * H / W
     f3 upU;                    // normalize(cross(right, fwd))
     f3 F;                      // normalize(fwd.x, fwd.y, 0): the panorama's centre column
     float aperture, focus, ortho_width;
@@ -47,10 +47,9 @@ inline int validate(const pt_camera* c) {
     return PT_OK;
 }
 
-// TWIN: pt_set_camera (pt_render.hip) through ptq::camera_basis, for {pos, fwd, right, upS}.
 inline Prepared prepare(const pt_camera& c) {
     float b[12];
-    ptq::camera_basis(c.cam, c.width, c.height, b);
+    pti::camera_basis(c.cam, c.width, c.height, b);
     Prepared p;
     p.model = c.model, p.W = c.width, p.H = c.height, p.flags = c.flags;
     p.fW = (float)c.width, p.fH = (float)c.height, p.rW = 1.0f / p.fW, p.rH = 1.0f / p.fH;
@@ -74,8 +73,8 @@ PT_HD void make_ray(const Prepared& c, int x, int y, uint32_t& state, f3& o, f3&
         ax = pt::random01(state);
         ay = pt::random01(state);
     }
-    const float u = pt::div_mk((float)x + ax, c.fW, c.rW) - 0.5f;
-    const float v = pt::div_mk((float)y + ay, c.fH, c.rH) - 0.5f;
+    const float u = pti::film_coord((float)x + ax, c.fW, c.rW);
+    const float v = pti::film_coord((float)y + ay, c.fH, c.rH);
     if (model == PT_CAM_ORTHO) {
         o = (c.pos + c.right * (u * c.ortho_width)) + c.upS * (v * c.ortho_width);
         d = c.fwd;
@@ -87,8 +86,7 @@ PT_HD void make_ray(const Prepared& c, int x, int y, uint32_t& state, f3& o, f3&
         o = c.pos;
         d = pt::normalize(h * sa + mk(0.0f, 0.0f, -ca));
     } else {
-        // TWIN: ptq::pixel_ray (pt_query.h) and camera_ray (pt_render_phase.h): the un-normalised pinhole direction
-        const f3 D = (c.fwd + c.right * u) + c.upS * v;
+        const f3 D = pti::pinhole_dir(c.fwd, c.right, c.upS, u, v);
         if (model == PT_CAM_THIN_LENS) {
             const float u1 = pt::random01(state);
             const float u2 = pt::random01(state);

@@ -26,39 +26,25 @@ struct Guide {
     float z;
 };
 
-// TWIN: ptt::shade (pt_trace.h), its mode 2, mode 3 and mode 4 branches and its miss branch, with inc = 0, col = 1
-// (pt::length_gt_001(col) holds).  o, d: the segment's ray as cast.
+// (inc = 0, col = 1: the gate holds; the sky's inc + env * col is written out for ptt::shade's -0 and NaN.)  o, d: as cast.
 template <class Q, class S>
 PT_HD Guide guide_sample(const S& sc, const ptq::Hit& hit, f3 o, f3 d, int flags) {
     Guide g;
-    const f3 inc = mk(0, 0, 0), col = mk(1, 1, 1);
     if (hit.kind != PT_HIT_NONE) {
         g.n = (hit.n + mk(1, 1, 1)) * 0.5f;
-        float s = pt::length(hit.p - o);
-        float dist = 1.0f - pt::fsqrt(s + 1.0f) / (s + 1.0f);
-        g.z = dist * dist;
+        g.z = pti::depth_term(hit.p, o);
         const Q m0 = sc.mat(hit.mat, 0);
         g.a = mk(m0.x, m0.y, m0.z);
     } else {
-        f3 env = mk(0, 0, 0);
-        if (!(flags & PT_FLAG_NO_SKY)) {
-            f3 dir = pt::normalize(d);
-            float tt = 0.5f * (dir.z + 1.0f);
-            float omt = 1.0f - tt;
-            env = mk(omt * 1.0f + tt * 0.5f, omt * 1.0f + tt * 0.7f, omt * 1.0f + tt * 1.0f);
-        }
-        const f3 rgb = inc + env * col;
+        const f3 rgb = mk(0, 0, 0) + pti::sky(d, (flags & PT_FLAG_NO_SKY) != 0) * mk(1, 1, 1);
         g.n = rgb, g.a = rgb, g.z = rgb.x;
     }
     return g;
 }
 
-// TWIN: pti::accumulate (pt_isect.h), one colour component at frame `frame` with acc = (frame > 1).
+// One component of the running mean at frame `frame` (pti::accumulate_1), from nothing at frame 1.
 PT_HD float fold(float prev, float s, int frame) {
-    if (!(frame > 1)) return s;
-    float ff = (float)frame;
-    float w = (ff - 1.0f) / ff;
-    return prev * w + s / ff;
+    return frame > 1 ? pti::accumulate_1(prev, s, (float)frame) : s;
 }
 
 // The two guide quads (N.rgb, Z), (A.rgb, 0) with the sample of frame `frame` folded in.

@@ -1,7 +1,10 @@
-// pt_isect.h -- the per-ray arithmetic of the render kernels (box tests, triangle tests, the
-// running mean, the tonemap), host- and device-callable like pt_math.h: the kernels of
-// pt_render.hip run these functions, and tests/isect/isect_check.cpp and the CPU walk models
+// pt_isect.h -- the per-ray arithmetic of the render kernels (box tests, the guard, sphere and triangle
+// tests, the leaf's choice, the camera ray, the sky and the bounce, the running mean, the tonemap),
+// host- and device-callable like pt_math.h: the kernels of pt_render.hip and the ray-batch units
+// (pt_query.h, pt_trace.h, pt_camera.h, pt_film.h, with their host twins) run these functions, and
+// tests/isect/isect_check.cpp, the device twin (tests/device) and the CPU walk models
 // (tests/wide/wide_sim.cpp, tests/cull/window_cull_sim.cpp) run the same source on the host.
+// What the render still restates, and the compiler output that keeps it there: DESIGN.md §17.
 // Everything they call (pt_math.h, pt_cull.h, pt_wide.h) is pinned the same way.
 // Templated on the 16-byte quad type: the kernels pass float4, a host build ptp::Quad
 // (pt_scene_pack.h) -- any struct with float members x, y, z, w.
@@ -79,13 +82,17 @@ PT_HD Q mkq(float x, float y, float z, float w) {   // make_float4 for any quad 
     Q r{x, y, z, w};
     return r;
 }
+// one component: prev * ((ff - 1) / ff) + s / ff with ff = (float)frame
+PT_HD float accumulate_1(float prev, float s, float ff) {
+    float w = (ff - 1.0f) / ff;
+    return prev * w + s / ff;
+}
 template <class Q>
 PT_HD Q accumulate(Q prev, f3 rgb, int frame, bool acc) {
     if (!acc) return mkq<Q>(rgb.x, rgb.y, rgb.z, 1.0f);
     float ff = (float)frame;
-    float w = (ff - 1.0f) / ff;
-    return mkq<Q>(prev.x * w + rgb.x / ff, prev.y * w + rgb.y / ff, prev.z * w + rgb.z / ff,
-                  prev.w * w + 1.0f / ff);
+    return mkq<Q>(accumulate_1(prev.x, rgb.x, ff), accumulate_1(prev.y, rgb.y, ff), accumulate_1(prev.z, rgb.z, ff),
+                  accumulate_1(prev.w, 1.0f, ff));
 }
 
 PT_HD float qdiv(float a, float b, float rb) {
@@ -158,6 +165,38 @@ PT_HD int oct_base(f3 d, int img_bytes) {
     return (int)o * img_bytes;
 }
 
+// The ray half of the exact-reciprocal guard with the scene half (ptp::SceneFacts::scene_fast): every origin component 0
+// or in [2^-40, 2^60], every direction component in [2^-20, 2] (NaN fails).  No short-circuit: each && was an exec-mask
+// branch.  ref::in_guard (tests/ref_walk.h) is the reference of its device-twin family.
+PT_HD bool ray_in_guard(bool scene_fast, f3 o, f3 d) {
+    return scene_fast & pt::in_guard(o.x, 0x1p-40f, 0x1p60f) & pt::in_guard(o.y, 0x1p-40f, 0x1p60f) &
+           pt::in_guard(o.z, 0x1p-40f, 0x1p60f) & pt::in_range_abs(d.x, 0x1p-20f, 2.0f) &
+           pt::in_range_abs(d.y, 0x1p-20f, 2.0f) & pt::in_range_abs(d.z, 0x1p-20f, 2.0f);
+}
+
+// hit_sphere (computeShader.c:209-226) of the sphere whose quad 0 is s0 = {centre, r^2}: the distance along o + d*t, or
+// -1 (the caller keeps the closest in (1e-4, t)).
+template <class Q>
+PT_HD float sphere_t(Q s0, f3 o, f3 d) {
+    f3 oc = o - mk(s0.x, s0.y, s0.z);
+    float a = pt::dot(d, d);
+    float half_b = pt::dot(oc, d);
+    float cq = pt::dot(oc, oc) - s0.w;
+    float disc = half_b * half_b - a * cq;
+    // the IEEE division sequence, not div_g: its range guard's four compares
+    // cost more than the sequence (same quotient; +0.6% on C2, round 5)
+    return disc < 0.0f ? -1.0f : (-half_b - pt::sqrt_g(disc)) / a;
+}
+
+// A leaf's 2-way choice (:406-429) between its triangles' hits h1, h2 (-1: a miss) against the segment's t.
+struct LeafChoice { bool c1, c2; };
+PT_HD LeafChoice leaf_choice(float h1, float h2, float t) {
+    const bool c1 = pt::win_open(h1, t) & ((h1 < h2) | (h2 < 0.0001f));
+    const bool c2 = !c1 & pt::win_open(h2, t);
+    const LeafChoice r = {c1, c2};
+    return r;
+}
+
 // hit_triangle split in two for the leaf phase's edge-test compaction: the plane distance
 // (:285-297) and the three edge tests at that distance (:299-306), the same operations as
 // tri_hit_bf in the same order, so the same bits.
@@ -182,6 +221,97 @@ PT_HD bool pair_in_window(Q nda, Q ndb, bool cop, f3 o, f3 d, float t0) {
     const float ta = tri_plane(nda, o, d);
     const float tb = cop ? ta : tri_plane(ndb, o, d);
     return pt::win_open(ta, t0) | pt::win_closed(tb, t0);
+}
+
+// ------------------------------------------------------------------ camera and shade
+// The camera basis (computeShader.c:519-522): {pos, fwd, right, up} from the camera floats {position.xyzw, direction.xyzw,
+// data.xyzw}, once per dispatch on the host in the pinned operations the shader performs per invocation.  Host only.
+inline void camera_basis(const float cam[12], int W, int H, float out[12]) {
+    const f3 pos = mk(cam[0], cam[1], cam[2]);
+    const f3 fwd = pt::normalize(mk(cam[4], cam[5], cam[6]));
+    const f3 right = pt::normalize(pt::cross(fwd, mk(0, 0, 1)));
+    const f3 up = (pt::normalize(pt::cross(right, fwd)) * (float)H) / (float)W;
+    const float v[12] = {pos.x, pos.y, pos.z, fwd.x, fwd.y, fwd.z, right.x, right.y, right.z, up.x, up.y, up.z};
+    for (int i = 0; i < 12; i++) out[i] = v[i];
+}
+
+// The film coordinate (x + jitter) / W - 0.5 of a pixel (:536-537) by rW = RN(1/W) and a Markstein correction: the
+// numerator is 0 or in [2^-32, 2^17), W <= 2^16, so the quotient is correctly rounded (tests/test_exact_div.py).
+PT_HD float film_coord(float px, float fW, float rW) { return pt::div_mk(px, fW, rW) - 0.5f; }
+// The un-normalised pinhole direction (:539) at film coordinates (u, v).
+PT_HD f3 pinhole_dir(f3 fwd, f3 right, f3 up, float u, float v) { return (fwd + right * u) + up * v; }
+
+// The sky of a ray that left the scene (getEnvironmentLight, :131-140), black under PT_FLAG_NO_SKY (`no_sky`).  d by
+// reference: by value the camera and film units' kernels commute one add.
+PT_HD f3 sky(const f3& d, bool no_sky) {
+    f3 env = mk(0, 0, 0);
+    if (!no_sky) {
+        f3 dir = pt::normalize(d);
+        float tt = 0.5f * (dir.z + 1.0f);
+        float omt = 1.0f - tt;
+        env = mk(omt * 1.0f + tt * 0.5f, omt * 1.0f + tt * 0.7f, omt * 1.0f + tt * 1.0f);
+    }
+    return env;
+}
+
+// The grey of display mode 4 (:461-463) for a hit at hitp seen from o.
+PT_HD float depth_term(f3 hitp, f3 o) {
+    float s = pt::length(hitp - o);
+    float dist = 1.0f - pt::fsqrt(s + 1.0f) / (s + 1.0f);
+    return dist * dist;
+}
+
+// The two directions of a bounce (:468-471) off a surface with `normal` (flipped against d): the diffuse one takes its
+// three normal draws from state, the specular one is reflect(d, normal), both normalised.
+PT_HD void bounce_dirs(f3 normal, f3 d, uint32_t& state, f3& diffuse, f3& specular) {
+    diffuse = pt::normalize(normal + pt::random_unit_vector(state));
+    float kk = 2.0f * pt::dot(normal, d);
+    specular = pt::normalize(d - normal * kk);
+}
+
+// The rest of the bounce (:483-493, and the loop's bound :447) from the material's quads m0 = {colour, smoothness},
+// m1 = {emission, specular probability}, m2 = {specular colour}.  Returns whether the path ended at max_bounce, with its
+// colour in rgb.  The quads come by value: read in here, by pointer or accessor, they move the render's assembly (§17).
+template <class Q>
+PT_HD bool bounce_mix(Q m0, Q m1, Q m2, f3 diffuse, f3 specular, int max_bounce, f3& d, f3& inc, f3& col, uint32_t& state,
+                      int& bounce, f3& rgb) {
+    float is_spec = (m1.w > pt::random01(state)) ? 1.0f : 0.0f;
+    d = pt::mix(diffuse, specular, m0.w * is_spec);
+    inc = inc + mk(m1.x, m1.y, m1.z) * col;
+    col = col * pt::mix(mk(m0.x, m0.y, m0.z), mk(m2.x, m2.y, m2.z), is_spec);
+    bounce++;
+    if (bounce > max_bounce) {
+        rgb = inc;
+        return true;
+    }
+    return false;
+}
+
+// A finished segment that hit a surface (Trace :452-493), from the hit point, the normal already flipped against d and
+// the material index: the return of display modes 2, 3 and 4, or the bounce.  Returns whether the path ended, with its
+// colour in rgb; otherwise o, d, inc, col, state and bounce are the next segment's.  sc.mat(i, k): quad k of material i.
+// TWIN: shade_segment (pt_render_phase.h) restates this dispatch around the same functions.
+template <class Q, class S>
+PT_HD bool shade_hit(const S& sc, int mat, f3 normal, f3 hitp, int mode, int max_bounce, f3& o, f3& d, f3& inc, f3& col,
+                     uint32_t& state, int& bounce, f3& rgb) {
+    if (mode == 2) {
+        rgb = (normal + mk(1, 1, 1)) * 0.5f;
+        return true;
+    }
+    if (mode == 4) {
+        float q = depth_term(hitp, o);
+        rgb = mk(q, q, q);
+        return true;
+    }
+    o = hitp;
+    f3 diffuse, specular;
+    bounce_dirs(normal, d, state, diffuse, specular);
+    const Q m0 = sc.mat(mat, 0), m1 = sc.mat(mat, 1), m2 = sc.mat(mat, 2);
+    if (mode == 3) {
+        rgb = mk(m0.x, m0.y, m0.z);
+        return true;
+    }
+    return bounce_mix(m0, m1, m2, diffuse, specular, max_bounce, d, inc, col, state, bounce, rgb);
 }
 
 // ACES film tonemap (screenQuadFrag.c:12-26) of one pixel -> RGBA8, alpha 255.

@@ -16,7 +16,7 @@ int pt_pixel_rays(int width, int height, const float cam[12], const int* xy, lon
     if (width <= 0 || height <= 0 || width > 65536 || height > 65536 || !cam || n < 0) return PT_E_ARG;
     if (n > 0 && (!xy || !rays_out)) return PT_E_ARG;
     float basis[12];
-    ptq::camera_basis(cam, width, height, basis);
+    pti::camera_basis(cam, width, height, basis);
     for (long long i = 0; i < n; i++) ptq::pixel_ray(basis, width, height, xy[2 * i], xy[2 * i + 1], &rays_out[i]);
     return PT_OK;
 }

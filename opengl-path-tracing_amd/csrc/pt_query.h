@@ -36,31 +36,14 @@ struct Hit {
 
 PT_HD int ibits(float f) { return (int)pt::fbits(f); }
 
-// The ray half of the exact-reciprocal guard with the scene half (SceneFacts::scene_fast).
-// TWIN: seg_in_guard (pt_render_phase.h), a device section of the render translation unit.
-// A segment of a render starts at t = +inf; a query's t_max is the caller's, so the guard also asks that it is not a
-// NaN (min_tf_t orders numbers only).  For every other t_max, of either sign, slab and slab_fast agree as they do
-// for a render's t: t enters both in one last compare.
+// The guard of a query: pti::ray_in_guard, and a t_max that is not a NaN (the caller's; min_tf_t orders numbers only).
+// For every other t_max, of either sign, slab and slab_fast agree as for a render's t: it enters both in one last compare.
 PT_HD bool ray_in_guard(bool scene_fast, f3 o, f3 d, float t_max) {
-    return scene_fast & pt::in_guard(o.x, 0x1p-40f, 0x1p60f) & pt::in_guard(o.y, 0x1p-40f, 0x1p60f) &
-           pt::in_guard(o.z, 0x1p-40f, 0x1p60f) & pt::in_range_abs(d.x, 0x1p-20f, 2.0f) &
-           pt::in_range_abs(d.y, 0x1p-20f, 2.0f) & pt::in_range_abs(d.z, 0x1p-20f, 2.0f) & (t_max == t_max);
-}
-
-// hit_sphere (:209-226): the distance along o + d*t, or -1.
-// TWIN: sphere_t (pt_render_phase.h).
-template <class Q>
-PT_HD float sphere_t(Q s0, f3 o, f3 d) {
-    f3 oc = o - mk(s0.x, s0.y, s0.z);
-    float a = pt::dot(d, d);
-    float half_b = pt::dot(oc, d);
-    float cq = pt::dot(oc, oc) - s0.w;
-    float disc = half_b * half_b - a * cq;
-    return disc < 0.0f ? -1.0f : (-half_b - pt::sqrt_g(disc)) / a;
+    return pti::ray_in_guard(scene_fast, o, d) & (t_max == t_max);
 }
 
 // The three edge tests (:299-306) at p with normal n.
-// TWIN: tri_edges_at (pt_render_sm.h).
+// TWIN: tri_edges_at (pt_render_sm.h), whose remark says why the render keeps its own.
 template <class Q>
 PT_HD bool tri_edges(Q q1, Q q2, Q q3, f3 n, f3 p) {
     const f3 v0 = mk(q1.x, q1.y, q1.z), v1 = mk(q2.x, q2.y, q2.z), v2 = mk(q3.x, q3.y, q3.z);
@@ -92,7 +75,7 @@ PT_HD Hit cast(const S& sc, f3 o, f3 d, float t_max, int flags, bool any_hit) {
     bool done = false;
     if (!(flags & PT_FLAG_NO_SPHERES)) {
         for (int si = 0; si < sc.n_spheres() && !done; si++) {
-            const float ht = sphere_t(sc.sphere(si, 0), o, d);
+            const float ht = pti::sphere_t(sc.sphere(si, 0), o, d);
             if ((ht > 0.0001f) & (ht < t)) {
                 t = ht;
                 kind = PT_HIT_SPHERE;
@@ -124,6 +107,7 @@ PT_HD Hit cast(const S& sc, f3 o, f3 d, float t_max, int flags, bool any_hit) {
                     h1 = tri_hit<Q>(sc, s0, o, d, t, false);
                     h2 = tri_hit<Q>(sc, s0 + 1, o, d, t, true);
                 }
+                // TWIN: pti::leaf_choice (pt_isect.h), kept written out in this association
                 const bool c1 = (h1 > 0.0001f) & (h1 < t) & ((h1 < h2) | (h2 < 0.0001f));
                 const bool c2 = !c1 & (h2 > 0.0001f) & (h2 < t);
                 if (c1 | c2) {
@@ -162,27 +146,14 @@ PT_HD Hit cast(const S& sc, f3 o, f3 d, float t_max, int flags, bool any_hit) {
     return h;
 }
 
-// The camera basis as pt_set_camera derives it (computeShader.c:519-522): {pos, fwd, right, up} from the 12 camera
-// floats {position.xyzw, direction.xyzw, data.xyzw}.
-// TWIN: pt_set_camera (pt_render.hip).
-inline void camera_basis(const float cam[12], int W, int H, float out[12]) {
-    const f3 pos = mk(cam[0], cam[1], cam[2]);
-    const f3 fwd = pt::normalize(mk(cam[4], cam[5], cam[6]));
-    const f3 right = pt::normalize(pt::cross(fwd, mk(0, 0, 1)));
-    const f3 up = (pt::normalize(pt::cross(right, fwd)) * (float)H) / (float)W;
-    const float v[12] = {pos.x, pos.y, pos.z, fwd.x, fwd.y, fwd.z, right.x, right.y, right.z, up.x, up.y, up.z};
-    for (int i = 0; i < 12; i++) out[i] = v[i];
-}
-
-// The camera ray of pixel (x, y) as a render with PT_FLAG_NO_AA forms it (:536-540), from the basis above.
-// TWIN: camera_ray (pt_render_phase.h), with zero jitter.
+// The camera ray of pixel (x, y) as a render with PT_FLAG_NO_AA forms it (:536-540), from pti::camera_basis's basis.
 inline void pixel_ray(const float basis[12], int W, int H, int x, int y, pt_ray* r) {
     const float fW = (float)W, fH = (float)H, rW = 1.0f / fW, rH = 1.0f / fH;
     const f3 pos = mk(basis[0], basis[1], basis[2]), fwd = mk(basis[3], basis[4], basis[5]);
     const f3 right = mk(basis[6], basis[7], basis[8]), up = mk(basis[9], basis[10], basis[11]);
-    const float u = pt::div_mk((float)x + 0.0f, fW, rW) - 0.5f;
-    const float v = pt::div_mk((float)y + 0.0f, fH, rH) - 0.5f;
-    const f3 d = pt::normalize((fwd + right * u) + up * v);
+    const float u = pti::film_coord((float)x + 0.0f, fW, rW);
+    const float v = pti::film_coord((float)y + 0.0f, fH, rH);
+    const f3 d = pt::normalize(pti::pinhole_dir(fwd, right, up, u, v));
     r->o[0] = pos.x, r->o[1] = pos.y, r->o[2] = pos.z, r->t_max = __builtin_huge_valf();
     r->d[0] = d.x, r->d[1] = d.y, r->d[2] = d.z, r->pad = 0.0f;
 }

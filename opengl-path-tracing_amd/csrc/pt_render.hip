@@ -240,14 +240,7 @@ int pt_upload_scene(pt_ctx* c, const float* tris, int n_tris, const float* bvh, 
 
 int pt_set_camera(pt_ctx* c, const float cam[12]) {
     if (!c || !cam) return PT_E_ARG;
-    // camera basis (computeShader.c:519-522), evaluated once per dispatch on the host with
-    // the same pinned binary32 ops the shader performs per invocation.
-    f3 pos = mk(cam[0], cam[1], cam[2]);
-    f3 fwd = pt::normalize(mk(cam[4], cam[5], cam[6]));
-    f3 right = pt::normalize(pt::cross(fwd, mk(0, 0, 1)));
-    f3 up = (pt::normalize(pt::cross(right, fwd)) * (float)c->cfg.height) / (float)c->cfg.width;
-    float v[12] = {pos.x, pos.y, pos.z, fwd.x, fwd.y, fwd.z, right.x, right.y, right.z, up.x, up.y, up.z};
-    std::memcpy(c->cam, v, sizeof(v));
+    pti::camera_basis(cam, c->cfg.width, c->cfg.height, c->cam);
     c->cam_ok = true;
     c->guides_ok = false;         // ... or of the old camera
     drop_graph(c);

@@ -75,6 +75,8 @@ __device__ __forceinline__ void stage_tris_chain_order(float4* dst, const KParam
 // SHADE, a finished segment (Trace :434-501): the surface bounce of the hit (hprim >= 0: triangle slot, <= -2: sphere
 // -2 - index, at o + d*t) or the sky.  Returns whether the path ended, with its colour in rgb; otherwise o, d, inc,
 // col, state and bounce are the next segment's.
+// TWIN: pti::shade_hit (pt_isect.h) is this dispatch on the display mode with the materials read through a scene
+// accessor; here they are read in place and only the arithmetic is pt_isect.h's (DESIGN.md §17 has the compiler output).
 template <bool LDS, class Facts>
 __device__ __forceinline__ bool shade_segment(const Facts& F, const KParams& p, const SceneView& S, bool hit, int hprim,
                                               float t, f3& o, f3& d, f3& inc, f3& col, uint32_t& state, int& bounce,
@@ -100,41 +102,23 @@ __device__ __forceinline__ bool shade_segment(const Facts& F, const KParams& p, 
             rgb = (normal + mk(1, 1, 1)) * 0.5f;
             finished = true;
         } else if (F.mode() == 4) {
-            float s = pt::length(hitp - o);
-            float dist = 1.0f - pt::fsqrt(s + 1.0f) / (s + 1.0f);
-            float q = dist * dist;
+            float q = pti::depth_term(hitp, o);
             rgb = mk(q, q, q);
             finished = true;
         } else {
             o = hitp;
-            f3 diffuse = pt::normalize(normal + pt::random_unit_vector(state));
-            float kk = 2.0f * pt::dot(normal, d);
-            f3 specular = pt::normalize(d - normal * kk);
+            f3 diffuse, specular;
+            pti::bounce_dirs(normal, d, state, diffuse, specular);
             float4 m0 = S.mats[3 * mat], m1 = S.mats[3 * mat + 1], m2 = S.mats[3 * mat + 2];
             if (F.mode() == 3) {
                 rgb = mk(m0.x, m0.y, m0.z);
                 finished = true;
             } else {
-                float is_spec = (m1.w > pt::random01(state)) ? 1.0f : 0.0f;
-                d = pt::mix(diffuse, specular, m0.w * is_spec);
-                inc = inc + mk(m1.x, m1.y, m1.z) * col;
-                col = col * pt::mix(mk(m0.x, m0.y, m0.z), mk(m2.x, m2.y, m2.z), is_spec);
-                bounce++;
-                if (bounce > p.max_bounce) {
-                    rgb = inc;
-                    finished = true;
-                }
+                finished = pti::bounce_mix(m0, m1, m2, diffuse, specular, p.max_bounce, d, inc, col, state, bounce, rgb);
             }
         }
     } else {
-        f3 env = mk(0, 0, 0);
-        if (!(F.flags() & PT_FLAG_NO_SKY)) {
-            f3 dir = pt::normalize(d);
-            float tt = 0.5f * (dir.z + 1.0f);
-            float omt = 1.0f - tt;
-            env = mk(omt * 1.0f + tt * 0.5f, omt * 1.0f + tt * 0.7f, omt * 1.0f + tt * 1.0f);
-        }
-        rgb = inc + env * col;
+        rgb = inc + pti::sky(d, (F.flags() & PT_FLAG_NO_SKY) != 0) * col;
         finished = true;
     }
     return finished;
@@ -183,39 +167,24 @@ __device__ __forceinline__ void camera_ray(const Facts& F, const KParams& p, f3 
         ax = pt::random01(state);
         ay = pt::random01(state);
     }
-    // (x + jitter) / W by the exact reciprocal RN(1/W) and a Markstein
-    // correction: the numerator is 0 or in [2^-32, 2^17), W <= 2^16, so the
-    // remainder is exact and the quotient correctly rounded (test_exact_div)
-    float u = pt::div_mk((float)lx + ax, p.fW, p.rW) - 0.5f;
-    float v = pt::div_mk((float)y + ay, p.fH, p.rH) - 0.5f;
-    d = pt::normalize((cfwd + cright * u) + cup * v);
+    float u = pti::film_coord((float)lx + ax, p.fW, p.rW);
+    float v = pti::film_coord((float)y + ay, p.fH, p.rH);
+    d = pt::normalize(pti::pinhole_dir(cfwd, cright, cup, u, v));
     o = cpos;
     inc = mk(0, 0, 0);
     col = mk(1, 1, 1);
     bounce = 0;
 }
 
-// The ray half of the exact-reciprocal guard, with the scene half (F.scene_fast()), evaluated without short-circuit
-// branches (each && of the old form was an exec-mask branch): every origin component 0 or in [2^-40, 2^60], every
-// direction component in [2^-20, 2] (NaN fails).
+// The segment's verdict of the exact-reciprocal guard (pti::ray_in_guard) with the launch's scene half.
 template <class Facts>
 __device__ __forceinline__ bool seg_in_guard(const Facts& F, f3 o, f3 d) {
-    return F.scene_fast() & in_guard(o.x, 0x1p-40f, 0x1p60f) & in_guard(o.y, 0x1p-40f, 0x1p60f) &
-           in_guard(o.z, 0x1p-40f, 0x1p60f) & in_range_abs(d.x, 0x1p-20f, 2.0f) &
-           in_range_abs(d.y, 0x1p-20f, 2.0f) & in_range_abs(d.z, 0x1p-20f, 2.0f);
+    return pti::ray_in_guard(F.scene_fast(), o, d);
 }
 
-// hit_sphere (:209-226) of sphere si: the distance along o + d*t, or -1 (the caller keeps the closest in (1e-4, t)).
+// hit_sphere of sphere si (pti::sphere_t).
 __device__ __forceinline__ float sphere_t(const SceneView& S, int si, f3 o, f3 d) {
-    float4 s0 = S.spheres[2 * si];
-    f3 oc = o - mk(s0.x, s0.y, s0.z);
-    float a = pt::dot(d, d);
-    float half_b = pt::dot(oc, d);
-    float cq = pt::dot(oc, oc) - s0.w;
-    float disc = half_b * half_b - a * cq;
-    // the IEEE division sequence, not div_g: its range guard's four compares
-    // cost more than the sequence (same quotient; +0.6% on C2, round 5)
-    return disc < 0.0f ? -1.0f : (-half_b - pt::sqrt_g(disc)) / a;
+    return pti::sphere_t(S.spheres[2 * si], o, d);
 }
 
 // The leaf sweep of a new segment inside the guard (`on`): its candidate leaves at this t, lowest bit first.
@@ -259,13 +228,7 @@ __device__ __forceinline__ unsigned sweep_candidates_signed(const KParams& p, co
     return cand;
 }
 
-// A leaf's 2-way choice (:406-429) between its triangles' hits h1, h2 (-1: a miss) against the segment's t.
-struct LeafChoice { bool c1, c2; };
-__device__ __forceinline__ LeafChoice leaf_choice(float h1, float h2, float t) {
-    const bool c1 = win_open(h1, t) & ((h1 < h2) | (h2 < 0.0001f));
-    const bool c2 = !c1 & win_open(h2, t);
-    const LeafChoice r = {c1, c2};
-    return r;
-}
+using pti::LeafChoice;   // a leaf's 2-way choice (pt_isect.h)
+using pti::leaf_choice;
 
 }  // namespace

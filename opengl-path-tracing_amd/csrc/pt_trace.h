@@ -26,57 +26,15 @@ PT_HD uint32_t pixel_seed(int x, int y) { return (uint32_t)y * 831266u + (uint32
 
 // A finished segment (Trace :434-501) from the hit record ptq::cast returned for it: Hit::n is the flipped normal,
 // Hit::p is o + d*t, Hit::mat the material.  Returns whether the path ended, with its colour in rgb; otherwise o, d,
-// inc, col, state and bounce are the next segment's.
-// TWIN: shade_segment (pt_render_phase.h), a device section of the render translation unit.
+// inc, col, state and bounce are the next segment's.  The pieces are pti::shade_hit and pti::sky (pt_isect.h).
 template <class Q, class S>
 PT_HD bool shade(const S& sc, const ptq::Hit& hit, f3& o, f3& d, f3& inc, f3& col, uint32_t& state, int& bounce,
                  int max_bounce, int mode, int flags, f3& rgb) {
-    bool finished = false;
     rgb = inc;
-    if (hit.kind != PT_HIT_NONE && pt::length_gt_001(col)) {
-        const f3 hitp = hit.p, normal = hit.n;
-        if (mode == 2) {
-            rgb = (normal + mk(1, 1, 1)) * 0.5f;
-            finished = true;
-        } else if (mode == 4) {
-            float s = pt::length(hitp - o);
-            float dist = 1.0f - pt::fsqrt(s + 1.0f) / (s + 1.0f);
-            float q = dist * dist;
-            rgb = mk(q, q, q);
-            finished = true;
-        } else {
-            o = hitp;
-            f3 diffuse = pt::normalize(normal + pt::random_unit_vector(state));
-            float kk = 2.0f * pt::dot(normal, d);
-            f3 specular = pt::normalize(d - normal * kk);
-            const Q m0 = sc.mat(hit.mat, 0), m1 = sc.mat(hit.mat, 1), m2 = sc.mat(hit.mat, 2);
-            if (mode == 3) {
-                rgb = mk(m0.x, m0.y, m0.z);
-                finished = true;
-            } else {
-                float is_spec = (m1.w > pt::random01(state)) ? 1.0f : 0.0f;
-                d = pt::mix(diffuse, specular, m0.w * is_spec);
-                inc = inc + mk(m1.x, m1.y, m1.z) * col;
-                col = col * pt::mix(mk(m0.x, m0.y, m0.z), mk(m2.x, m2.y, m2.z), is_spec);
-                bounce++;
-                if (bounce > max_bounce) {
-                    rgb = inc;
-                    finished = true;
-                }
-            }
-        }
-    } else {
-        f3 env = mk(0, 0, 0);
-        if (!(flags & PT_FLAG_NO_SKY)) {
-            f3 dir = pt::normalize(d);
-            float tt = 0.5f * (dir.z + 1.0f);
-            float omt = 1.0f - tt;
-            env = mk(omt * 1.0f + tt * 0.5f, omt * 1.0f + tt * 0.7f, omt * 1.0f + tt * 1.0f);
-        }
-        rgb = inc + env * col;
-        finished = true;
-    }
-    return finished;
+    if (hit.kind != PT_HIT_NONE && pt::length_gt_001(col))
+        return pti::shade_hit<Q>(sc, hit.mat, hit.n, hit.p, mode, max_bounce, o, d, inc, col, state, bounce, rgb);
+    rgb = inc + pti::sky(d, (flags & PT_FLAG_NO_SKY) != 0) * col;
+    return true;
 }
 
 // What a launch holds for every ray: the context's settings and the frames asked for.

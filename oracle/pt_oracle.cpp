@@ -602,6 +602,9 @@ float oracle_hit_triangle(const float* o, const float* d, const float* tri, floa
     normal[0] = n.x; normal[1] = n.y; normal[2] = n.z;
     return t;
 }
+float oracle_hit_sphere(const float* o, const float* d, const float* sphere) {   // sphere: {centre, radius}
+    return hit_sphere(v3(o[0], o[1], o[2]), v3(d[0], d[1], d[2]), sphere);
+}
 float oracle_cosf(float x) { return o_cosf(x); }
 
 // Batch forms for exhaustive checks.

@@ -73,7 +73,7 @@ Out sweep_walk(unsigned mask, f3 o, f3 d, f3 rd, float t0) {
 
 void segment(f3 o, f3 d, Acc& A, float* t_out, int* tri_out) {
     const float t0 = sphere_t(o, d);
-    const bool guarded = in_guard(o, d);
+    const bool guarded = pti::ray_in_guard(true, o, d);   // the kernel's own verdict
     unsigned on = 0u, off = 0u, full = 0u;
     f3 rd = mk(0, 0, 0), ol, oh;
     if (guarded) {   // the kernel's segment set-up, as for a camera outside the root box: the root's test first

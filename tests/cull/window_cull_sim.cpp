@@ -118,7 +118,7 @@ Out cull_walk(f3 o, f3 d, float t0, const CRay& cr, float c_lo) {
 
 void segment(f3 o, f3 d, Acc& A, float* t_out, int* tri_out) {
     const float t0 = sphere_t(o, d);
-    const bool guarded = in_guard(o, d);
+    const bool guarded = pti::ray_in_guard(true, o, d);   // the kernel's own verdict
     CRay cr{};
     if (guarded) cr = make_ray(o, d);
     const Out ro = checked_ref_walk(o, d, t0, guarded, cr, A);

@@ -137,6 +137,12 @@ int main(int argc, char** argv) {
     family<twf::WideNext>(C.wide_next);
     family<twf::Rng>(C.rng);
     family<twf::Vec>(C.vec);
+    family<twf::Guard>(C.guard);
+    family<twf::Sphere>(C.sphere);
+    family<twf::LeafChoice>(C.leaf_choice);
+    family<twf::Pinhole>(C.pinhole);
+    family<twf::SkyDepth>(C.sky_depth);
+    family<twf::Bounce>(C.bounce);
 
     const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::printf("{\"done\": true, \"mismatches\": %ld, \"seconds\": %.2f}\n", g_bad, s);

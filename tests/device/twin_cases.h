@@ -1,7 +1,8 @@
 // TEST INFRASTRUCTURE: the cases of the device twin (tests/device/device_twin.hip) beyond those of
 // tests/isect/isect_cases.h: boxes and rays outside every guard for pti::slab, the culling test and the
-// leaf sweep (pt_cull.h), the noise estimate (pt_noise.h), the wide walk (pt_wide.h) and the guarded
-// forms and the RNG of pt_math.h.  Plain C++, no HIP: tests/device/twin_host.cpp runs them on the CPU.
+// leaf sweep (pt_cull.h), the noise estimate (pt_noise.h), the wide walk (pt_wide.h), the guarded
+// forms and the RNG of pt_math.h, and the per-ray arithmetic the render shares with the ray-batch units
+// (pt_isect.h: the guard, the sphere distance, the leaf's choice, the camera ray, the sky and the bounce).  Plain C++, no HIP: tests/device/twin_host.cpp runs them on the CPU.
 // Every generator seeds the stream itself, so its cases do not depend on what ran before it, and no expression draws
 // twice, so they do not depend on the compiler either (isect_cases.h).
 #pragma once
@@ -12,6 +13,7 @@
 
 namespace twc {
 
+using isc::gcoord;
 using isc::mag;
 using isc::nx;
 using isc::sgn;
@@ -28,12 +30,14 @@ inline void reseed(uint64_t k) { isc::rs = isc::kSeed ^ (k * 0x9e3779b97f4a7c15u
 constexpr long kSlab = 2000003, kTri = 1000003, kAces = 1000003, kAccumPerFrame = 20003, kAccum = 10 * (long)kAccumPerFrame;
 constexpr long kSlabWild = 500009, kCull = 1000003, kSweepRays = 100003, kQuant = 300007, kTarget = 100003, kRetire = 100003;
 constexpr long kFold = 20011, kWideHits = 500009, kWideNext = 1000003, kRng = (1l << 20) + 3, kVec = 500009;
+constexpr long kGuard = 100003, kSphere = 100003, kLeafChoice = 100003, kPinhole = 100003, kSkyDepth = 100003, kBounce = 100003;
 constexpr int kSweepTables = 5;
 constexpr int kSweepN[kSweepTables] = {1, 2, 17, 24, 32};
 constexpr bool partial(long n) { return n % 64 != 0; }
 static_assert(partial(kSlab) && partial(kTri) && partial(kAces) && partial(kAccum) && partial(kSlabWild) && partial(kCull) &&
                   partial(kSweepRays) && partial(kQuant) && partial(kTarget) && partial(kRetire) && partial(kFold) &&
-                  partial(kWideHits) && partial(kWideNext) && partial(kRng) && partial(kVec),
+                  partial(kWideHits) && partial(kWideNext) && partial(kRng) && partial(kVec) && partial(kGuard) &&
+                  partial(kSphere) && partial(kLeafChoice) && partial(kPinhole) && partial(kSkyDepth) && partial(kBounce),
               "a partial last wave in every launch");
 
 // ------------------------------------------------------------------ slab_wild: pti::slab on any binary32
@@ -494,6 +498,246 @@ inline void vec_cases(long n, std::vector<VecCase>& out) {
         c.b = mk(bx, by, bz);
         if (nx() % 2) c.a.y = nx() % 2 ? edge_mag(e2) : any_mag();      // div_g(b.y, a.y): a denominator at the edge
         c.s = nx() % 8 == 0 ? (float)(nx() % 2) : uni();
+        out.push_back(c);
+    }
+}
+
+// ------------------------------------------------------------------ guard: pti::ray_in_guard
+// Domain: every binary32 in every component.  Most components lie inside their window, so that both verdicts are
+// frequent; the rest sit at and one ulp either side of the windows' ends (2^-40 and 2^60 for the origin, 2^-20 and 2
+// for the direction), or are zeros, NaNs, infinities and subnormals.
+struct GuardCase {
+    f3 o, d;
+    int scene_fast;
+};
+inline float guard_component(bool origin) {
+    const uint64_t kind = nx() % 16;
+    if (kind >= 3) return origin ? gcoord() : isc::dcoord();
+    if (kind == 0) {      // an end of the window, and one ulp either side
+        const float sg = sgn();
+        const float edge = nx() % 2 ? (origin ? 0x1p-40f : 0x1p-20f) : (origin ? 0x1p60f : 2.0f);
+        return sg * ulps(edge, (int)(nx() % 3) - 1);
+    }
+    if (kind == 1) {      // an end of the other kind of component's window
+        const float sg = sgn();
+        const float edge = nx() % 2 ? (origin ? 0x1p-20f : 0x1p-40f) : (origin ? 2.0f : 0x1p60f);
+        return sg * ulps(edge, (int)(nx() % 3) - 1);
+    }
+    const float v[] = {0.0f, -0.0f, NAN, -NAN, INFINITY, -INFINITY, 0x1p-149f, -0x1p-126f};
+    return v[nx() % 8];
+}
+inline void guard_cases(long n, std::vector<GuardCase>& out) {
+    reseed(11);
+    for (long k = 0; k < n; k++) {
+        GuardCase c;
+        const float oz = guard_component(true), oy = guard_component(true), ox = guard_component(true);
+        const float dz = guard_component(false), dy = guard_component(false), dx = guard_component(false);
+        c.o = mk(ox, oy, oz);
+        c.d = mk(dx, dy, dz);
+        c.scene_fast = nx() % 8 != 0;
+        out.push_back(c);
+    }
+}
+
+// ------------------------------------------------------------------ sphere: pti::sphere_t
+// Domain: any ray, a sphere with a finite centre and radius r >= 0, stored as the packer stores it ({centre, r * r}).
+// Rays that miss, that graze (a discriminant of exactly 0 on small integers, and one ulp of the centre either side
+// of it; tangent rays at any angle, whose discriminant is a few ulps from 0), that start inside the sphere or on it,
+// that point away, and rays with zero, NaN or infinite components.
+struct SphereCase {
+    float c[3], r;
+    f3 o, d;
+};
+inline void sphere_cases(long n, std::vector<SphereCase>& out) {
+    reseed(12);
+    for (long k = 0; k < n; k++) {
+        SphereCase c;
+        const float s = std::ldexp(1.0f, (int)(nx() % 33) - 16);
+        const uint64_t kind = nx() % 8;
+        if (kind == 0) {            // small integers along one axis: a = 1, disc = j^2 - (j^2 + m^2 - r^2) exactly
+            const int axis = (int)(nx() % 3), side = (axis + 1 + (int)(nx() % 2)) % 3;
+            const float j = (float)(1 + nx() % 64), m = (float)(nx() % 16);
+            float cv[3] = {0.0f, 0.0f, 0.0f}, ov[3] = {0.0f, 0.0f, 0.0f}, dv[3] = {0.0f, 0.0f, 0.0f};
+            cv[side] = ulps(m * s, (int)(nx() % 3) - 1);      // the centre m away from the ray's line, r = m: a graze
+            ov[axis] = -j * s;
+            dv[axis] = 1.0f;
+            for (int q = 0; q < 3; q++) c.c[q] = cv[q];
+            c.r = m * s;
+            c.o = mk(ov[0], ov[1], ov[2]);
+            c.d = mk(dv[0], dv[1], dv[2]);
+        } else {
+            const f3 ctr = isc::sym3(mk(0.0f, 0.0f, 0.0f), 4.0f * s);
+            c.c[0] = ctr.x, c.c[1] = ctr.y, c.c[2] = ctr.z;
+            c.r = s * (0.125f + uni());
+            uint32_t st = (uint32_t)nx();
+            const f3 u = pt::random_unit_vector(st);                 // the ray's direction
+            f3 w = pt::cross(u, mk(0.0f, 0.0f, 1.0f));
+            if (!(pt::dot(w, w) > 0.0f)) w = mk(1.0f, 0.0f, 0.0f);
+            w = pt::normalize(w);                                     // a unit vector across it
+            const float back = s * 8.0f * uni();
+            if (kind == 1) {        // tangent: the line passes at distance r (and one ulp of r either side)
+                const float rr = ulps(c.r, (int)(nx() % 3) - 1);
+                c.o = (ctr + w * rr) - u * back;
+                c.d = u;
+            } else if (kind == 2) { // the origin inside the sphere, or on it
+                const float f = nx() % 4 == 0 ? 1.0f : uni();
+                c.o = ctr + w * (c.r * f);
+                c.d = u;
+            } else if (kind == 3) { // aimed at the sphere from behind it: both roots negative
+                c.o = (ctr + w * (c.r * uni())) + u * (c.r + back);
+                c.d = u;
+            } else if (kind == 4) { // a wide miss
+                c.o = (ctr + w * (c.r * (1.0f + 4.0f * uni()))) - u * back;
+                c.d = u;
+            } else {                // a hit, the direction not normalised
+                const float len = nx() % 2 ? 1.0f : std::fabs(mag(-8, 8));
+                c.o = (ctr + w * (c.r * uni())) - u * (c.r + back);
+                c.d = u * len;
+            }
+            if (nx() % 32 == 0) {   // one component of the ray replaced
+                const float v[] = {0.0f, -0.0f, NAN, INFINITY, -INFINITY, 0x1p-149f, 0x1p127f, -0x1p-126f};
+                const float x = v[nx() % 8];
+                float* comp[6] = {&c.o.x, &c.o.y, &c.o.z, &c.d.x, &c.d.y, &c.d.z};
+                *comp[nx() % 6] = x;
+            }
+            if (nx() % 64 == 0) c.d = mk(0.0f, 0.0f, 0.0f);          // a = 0: 0/0 or x/0
+        }
+        out.push_back(c);
+    }
+}
+
+// ------------------------------------------------------------------ leaf_choice: pti::leaf_choice
+// Domain: every binary32 in h1, h2 and t.  Each is a distance of any scale, or sits at and one ulp either side of
+// 1e-4, of t and of the other hit, or is -1 (a miss), NaN or +inf.
+struct LeafChoiceCase {
+    float h1, h2, t;
+};
+inline float choice_value(float near_a, float near_b) {
+    switch (nx() % 8) {
+        case 0: return ulps(0.0001f, (int)(nx() % 3) - 1);
+        case 1: return ulps(near_a, (int)(nx() % 3) - 1);
+        case 2: return ulps(near_b, (int)(nx() % 3) - 1);
+        case 3: return -1.0f;
+        case 4: { const float v[] = {NAN, INFINITY, 0.0f, -0.0f, -INFINITY, 0x1p-149f}; return v[nx() % 6]; }
+        default: return std::fabs(mag(-16, 8));
+    }
+}
+inline void leaf_choice_cases(long n, std::vector<LeafChoiceCase>& out) {
+    reseed(13);
+    for (long k = 0; k < n; k++) {
+        LeafChoiceCase c;
+        const uint64_t tk = nx() % 8;
+        c.t = tk == 0 ? INFINITY : tk == 1 ? ulps(0.0001f, (int)(nx() % 3) - 1) : std::fabs(mag(-12, 8));
+        if (nx() % 64 == 0) c.t = NAN;
+        c.h1 = choice_value(c.t, 1.0f);
+        c.h2 = choice_value(c.t, c.h1);
+        if (nx() % 4 == 0) c.h1 = ulps(c.h2, (int)(nx() % 3) - 1);    // the first beside the second
+        out.push_back(c);
+    }
+}
+
+// ------------------------------------------------------------------ pinhole: pti::film_coord, pti::pinhole_dir
+// Domain: an image of 1..65536 pixels a side, a pixel of it, a jitter in {0} U [2^-32, 1) as pt::random01 gives it
+// (the numerator of film_coord is then 0 or in [2^-32, 2^17)), and a camera basis as pti::camera_basis derives it.
+struct PinholeCase {
+    int x, y, W, H;
+    float ax, ay, rW, rH;      // rW, rH: RN(1/W), RN(1/H) by the host's IEEE division, as every caller derives them
+    f3 fwd, right, up;
+};
+inline void pinhole_cases(long n, std::vector<PinholeCase>& out) {
+    reseed(14);
+    const int sizes[] = {1, 2, 3, 64, 640, 1000, 1920, 4096, 65535, 65536};
+    for (long k = 0; k < n; k++) {
+        PinholeCase c;
+        c.W = nx() % 4 == 0 ? sizes[nx() % 10] : 1 + (int)(nx() % 65536);
+        c.H = nx() % 4 == 0 ? sizes[nx() % 10] : 1 + (int)(nx() % 65536);
+        c.x = nx() % 8 == 0 ? c.W - 1 : (int)(nx() % (uint64_t)c.W);
+        c.y = nx() % 8 == 0 ? 0 : (int)(nx() % (uint64_t)c.H);
+        uint32_t st = (uint32_t)nx();
+        c.ax = nx() % 4 == 0 ? 0.0f : pt::random01(st);
+        c.ay = nx() % 4 == 0 ? 0.0f : pt::random01(st);
+        if (nx() % 16 == 0) c.ax = 0x1p-32f;
+        c.rW = 1.0f / (float)c.W, c.rH = 1.0f / (float)c.H;
+        const float dz = sym(), dy = sym(), dx = sym();
+        float cam[12] = {0.0f, 0.0f, 0.0f, 0.0f, dx, dy, dz, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, b[12];
+        pti::camera_basis(cam, c.W, c.H, b);
+        c.fwd = mk(b[3], b[4], b[5]), c.right = mk(b[6], b[7], b[8]), c.up = mk(b[9], b[10], b[11]);
+        out.push_back(c);
+    }
+}
+
+// ------------------------------------------------------------------ sky_depth: pti::sky, pti::depth_term
+// Domain: any direction (pt::normalize switches forms where dot(d, d) leaves [2^-100, 2^100]; zero and NaN
+// directions as a ray outside every guard has them), and a hit point and origin of any finite scale.
+struct SkyDepthCase {
+    f3 d, hitp, o;
+    int no_sky;
+};
+inline void sky_depth_cases(long n, std::vector<SkyDepthCase>& out) {
+    reseed(15);
+    for (long k = 0; k < n; k++) {
+        SkyDepthCase c;
+        const uint64_t kind = nx() % 8;
+        if (kind == 0) {            // dot(d, d) beside 2^-100 or 2^100
+            const int e = nx() % 2 ? -50 : 50;
+            uint32_t st = (uint32_t)nx();
+            c.d = pt::random_unit_vector(st) * std::ldexp(1.0f, e);
+        } else if (kind == 1) {     // straight up, down, level
+            const float z = nx() % 3 == 0 ? 0.0f : sgn();
+            const float x = z == 0.0f ? 1.0f : 0.0f;
+            c.d = mk(x, 0.0f, z);
+        } else if (kind == 2) {
+            const float v[] = {0.0f, -0.0f, NAN, INFINITY, -INFINITY, 0x1p-149f};
+            const float z = v[nx() % 6], y = nx() % 2 ? 0.0f : sym(), x = nx() % 2 ? 0.0f : sym();
+            c.d = mk(x, y, z);
+        } else {
+            uint32_t st = (uint32_t)nx();
+            const float len = nx() % 2 ? 1.0f : std::fabs(mag(-20, 20));
+            c.d = pt::random_unit_vector(st) * len;
+        }
+        const float s = std::ldexp(1.0f, (int)(nx() % 81) - 40);
+        c.o = isc::sym3(mk(0.0f, 0.0f, 0.0f), s);
+        const float far = nx() % 8 == 0 ? 0.0f : std::ldexp(1.0f, (int)(nx() % 41) - 20);
+        c.hitp = isc::sym3(c.o, s * far);                               // far = 0: the hit at the origin, s = 0
+        if (nx() % 64 == 0) c.hitp.x = nx() % 2 ? INFINITY : NAN;
+        c.no_sky = nx() % 8 == 0;
+        out.push_back(c);
+    }
+}
+
+// ------------------------------------------------------------------ bounce: pti::shade_hit
+// Domain: what a hit segment hands to the shade: a unit normal flipped against d, a direction of any length, a hit
+// point, gathered light >= 0 and a carried colour in [0, 1], any RNG state, a material of the twin's fixed table
+// (twf::TwinMats), all four display modes, bounce at, below and above max_bounce - 1.
+constexpr int kTwinMats = 6;
+struct BounceCase {
+    f3 normal, hitp, o, d, inc, col;
+    uint32_t state;
+    int bounce, max_bounce, mode, mat;
+};
+inline void bounce_cases(long n, std::vector<BounceCase>& out) {
+    reseed(32);
+    for (long k = 0; k < n; k++) {
+        BounceCase c;
+        uint32_t st = (uint32_t)nx();
+        c.normal = pt::random_unit_vector(st);
+        const float len = nx() % 4 == 0 ? std::fabs(mag(-6, 6)) : 1.0f;
+        c.d = pt::random_unit_vector(st) * len;
+        if (nx() % 16 == 0) c.d = c.normal * -len;                      // head on: the reflection is -d
+        if (nx() % 16 == 0) c.d = pt::cross(c.normal, c.d);             // grazing: dot(normal, d) about 0
+        if (pt::dot(c.normal, c.d) > 0.0f) c.normal = c.normal * -1.0f;
+        const float s = std::ldexp(1.0f, (int)(nx() % 25) - 12);
+        c.o = isc::sym3(mk(0.0f, 0.0f, 0.0f), s);
+        c.hitp = isc::sym3(c.o, s);
+        const float iz = 4.0f * uni(), iy = 4.0f * uni(), ix = 4.0f * uni();
+        c.inc = nx() % 4 == 0 ? mk(0.0f, 0.0f, 0.0f) : mk(ix, iy, iz);
+        const float cz = uni(), cy = uni(), cx = uni();
+        c.col = nx() % 4 == 0 ? mk(1.0f, 1.0f, 1.0f) : mk(cx, cy, cz);
+        c.state = k < 4 ? (uint32_t)(0u - (uint32_t)k) : (uint32_t)nx();
+        c.max_bounce = (int)(nx() % 9);
+        c.bounce = nx() % 2 ? c.max_bounce : (int)(nx() % (uint64_t)(c.max_bounce + 1));
+        c.mode = 1 + (int)(nx() % 4);
+        c.mat = (int)(nx() % (uint64_t)kTwinMats);
         out.push_back(c);
     }
 }

@@ -13,9 +13,11 @@
 #pragma once
 
 #include "twin_cases.h"
+#include "../ref_walk.h"
 
 #include <cstdio>
 
+extern "C" float oracle_hit_sphere(const float* o, const float* d, const float* sphere);
 extern "C" float oracle_hit_triangle(const float* o, const float* d, const float* tri, float* normal);
 extern "C" float oracle_mt_triangle(const float* o, const float* d, const float* tri, float* normal);
 
@@ -437,6 +439,148 @@ struct Vec {
     }
 };
 
+// ------------------------------------------------------------------ what the render shares with the ray-batch units
+struct Guard {
+    using Case = twc::GuardCase;
+    using Ctx = NoCtx;
+    static constexpr int W = 1;
+    static constexpr bool boolean = true, has_ref = true;
+    static const char* name() { return "guard"; }
+    PT_HD static void eval(const Case& c, const Ctx&, uint32_t* r) { r[0] = (uint32_t)pti::ray_in_guard(c.scene_fast != 0, c.o, c.d); }
+    // the float compares of tests/ref_walk.h against the bit-pattern windows
+    static void ref(const Case& c, const Ctx&, const uint32_t*, uint32_t* r) { r[0] = c.scene_fast != 0 && ref::in_guard(c.o, c.d); }
+    static bool positive(const Case&, const uint32_t* r) { return r[0] & 1u; }
+    static void nudge(Case& c) { c.d.x = step(c.d.x); c.o.y = step(c.o.y); }
+    static void show(const Case& c) {
+        std::fprintf(stderr, "o=(%a,%a,%a) d=(%a,%a,%a) scene_fast=%d", c.o.x, c.o.y, c.o.z, c.d.x, c.d.y, c.d.z, c.scene_fast);
+    }
+};
+struct Sphere {
+    using Case = twc::SphereCase;
+    using Ctx = NoCtx;
+    static constexpr int W = 1;   // t as a word
+    // boolean only in that its positives (a distance a segment at t = +inf takes) are held to the 1%-99% check
+    static constexpr bool boolean = true, has_ref = true;
+    static const char* name() { return "sphere"; }
+    PT_HD static void eval(const Case& c, const Ctx&, uint32_t* r) {
+        r[0] = fw(pti::sphere_t(Quad{c.c[0], c.c[1], c.c[2], c.r * c.r}, c.o, c.d));   // r * r: the packer's quad 0
+    }
+    static void ref(const Case& c, const Ctx&, const uint32_t*, uint32_t* r) {
+        const float ov[3] = {c.o.x, c.o.y, c.o.z}, dv[3] = {c.d.x, c.d.y, c.d.z}, sp[4] = {c.c[0], c.c[1], c.c[2], c.r};
+        r[0] = fw(oracle_hit_sphere(ov, dv, sp));
+    }
+    static bool positive(const Case&, const uint32_t* r) { return pt::bitsf(r[0]) > 0.0001f; }   // a hit a segment at t = +inf takes
+    static void nudge(Case& c) { c.o.x = step(c.o.x); c.o.y = step(c.o.y); }
+    static void show(const Case& c) {
+        std::fprintf(stderr, "c=(%a,%a,%a) r=%a o=(%a,%a,%a) d=(%a,%a,%a)", c.c[0], c.c[1], c.c[2], c.r, c.o.x, c.o.y, c.o.z, c.d.x, c.d.y, c.d.z);
+    }
+};
+struct LeafChoice {
+    using Case = twc::LeafChoiceCase;
+    using Ctx = NoCtx;
+    static constexpr int W = 1;
+    static constexpr bool boolean = true, has_ref = true;
+    static const char* name() { return "leaf_choice"; }
+    PT_HD static void eval(const Case& c, const Ctx&, uint32_t* r) {
+        const pti::LeafChoice lc = pti::leaf_choice(c.h1, c.h2, c.t);
+        r[0] = (uint32_t)lc.c1 | (uint32_t)lc.c2 << 1;
+    }
+    // the reference's two ifs (tests/ref_walk.h)
+    static void ref(const Case& c, const Ctx&, const uint32_t*, uint32_t* r) { r[0] = (uint32_t)ref::choose(c.h1, c.h2, c.t); }
+    static bool positive(const Case&, const uint32_t* r) { return r[0] != 0u; }
+    static void nudge(Case& c) { c.t = step(c.t); }
+    static void show(const Case& c) { std::fprintf(stderr, "h1=%a h2=%a t=%a", c.h1, c.h2, c.t); }
+};
+struct Pinhole {
+    using Case = twc::PinholeCase;
+    using Ctx = NoCtx;
+    static constexpr int W = 5;
+    static constexpr bool boolean = false, has_ref = true;
+    static const char* name() { return "pinhole"; }
+    PT_HD static void eval(const Case& c, const Ctx&, uint32_t* r) {
+        const float u = pti::film_coord((float)c.x + c.ax, (float)c.W, c.rW);
+        const float v = pti::film_coord((float)c.y + c.ay, (float)c.H, c.rH);
+        const f3 D = pti::pinhole_dir(c.fwd, c.right, c.up, u, v);
+        r[0] = fw(u), r[1] = fw(v), r[2] = fw(D.x), r[3] = fw(D.y), r[4] = fw(D.z);
+    }
+    // the film coordinates by the division the reference writes (:536-537) and the direction of :539, every
+    // operation computed in double and rounded once
+    static void ref(const Case& c, const Ctx&, const uint32_t*, uint32_t* r) {
+        const float u = isc::add32(isc::div32(isc::add32((float)c.x, c.ax), (float)c.W), -0.5f);
+        const float v = isc::add32(isc::div32(isc::add32((float)c.y, c.ay), (float)c.H), -0.5f);
+        const float f[3] = {c.fwd.x, c.fwd.y, c.fwd.z}, rt[3] = {c.right.x, c.right.y, c.right.z}, up[3] = {c.up.x, c.up.y, c.up.z};
+        r[0] = fw(u), r[1] = fw(v);
+        for (int q = 0; q < 3; q++) r[2 + q] = fw(isc::add32(isc::add32(f[q], isc::mul32(rt[q], u)), isc::mul32(up[q], v)));
+    }
+    static bool positive(const Case&, const uint32_t* r) { return pt::bitsf(r[0]) > 0.0f; }   // right of the centre column
+    static void nudge(Case& c) { c.x ^= 1; c.up.z = step(c.up.z); }
+    static void show(const Case& c) {
+        std::fprintf(stderr, "x=%d y=%d W=%d H=%d ax=%a ay=%a fwd=(%a,%a,%a) right=(%a,%a,%a) up=(%a,%a,%a)", c.x, c.y, c.W, c.H, c.ax, c.ay,
+                     c.fwd.x, c.fwd.y, c.fwd.z, c.right.x, c.right.y, c.right.z, c.up.x, c.up.y, c.up.z);
+    }
+};
+struct SkyDepth {
+    using Case = twc::SkyDepthCase;
+    using Ctx = NoCtx;
+    static constexpr int W = 4;
+    static constexpr bool boolean = false, has_ref = false;
+    static const char* name() { return "sky_depth"; }
+    PT_HD static void eval(const Case& c, const Ctx&, uint32_t* r) {
+        const f3 env = pti::sky(c.d, c.no_sky != 0);
+        r[0] = fw(env.x), r[1] = fw(env.y), r[2] = fw(env.z);
+        r[3] = fw(pti::depth_term(c.hitp, c.o));
+    }
+    static void ref(const Case&, const Ctx&, const uint32_t* self, uint32_t* r) {
+        for (int i = 0; i < W; i++) r[i] = self[i];
+    }
+    static bool positive(const Case& c, const uint32_t*) { return c.no_sky == 0; }
+    static void nudge(Case& c) { c.d.z = step(c.d.z); c.hitp.y = step(c.hitp.y); }
+    static void show(const Case& c) {
+        std::fprintf(stderr, "d=(%a,%a,%a) hitp=(%a,%a,%a) o=(%a,%a,%a) no_sky=%d", c.d.x, c.d.y, c.d.z, c.hitp.x, c.hitp.y, c.hitp.z, c.o.x,
+                     c.o.y, c.o.z, c.no_sky);
+    }
+};
+// the twin's material table: quads {colour, smoothness}, {emission, specular probability}, {specular colour, 0}
+struct TwinMats {
+    PT_HD Quad mat(int i, int k) const {
+        const float T[twc::kTwinMats][12] = {
+            {0.73f, 0.73f, 0.73f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 1.0f, 1.0f, 0.0f},          // diffuse white
+            {0.65f, 0.05f, 0.05f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 1.0f, 1.0f, 0.0f},          // diffuse red
+            {0.0f, 0.0f, 0.0f, 0.0f, 15.0f, 15.0f, 15.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f},          // a light
+            {0.9f, 0.9f, 0.9f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.95f, 0.95f, 0.95f, 0.0f},          // a mirror
+            {0.12f, 0.45f, 0.15f, 0.6f, 0.0f, 0.0f, 0.0f, 0.5f, 1.0f, 0.9f, 0.8f, 0.0f},          // glossy, half the bounces
+            {0.5f, 0.5f, 0.5f, 0.25f, 0.3f, 0.2f, 0.1f, 0x1p-32f, 0.5f, 0.5f, 0.5f, 0.0f}};       // specular at one draw only
+        return Quad{T[i][4 * k], T[i][4 * k + 1], T[i][4 * k + 2], T[i][4 * k + 3]};
+    }
+};
+struct Bounce {
+    using Case = twc::BounceCase;
+    using Ctx = NoCtx;
+    static constexpr int W = 18;
+    static constexpr bool boolean = false, has_ref = false;
+    static const char* name() { return "bounce"; }
+    PT_HD static void eval(const Case& c, const Ctx&, uint32_t* r) {
+        f3 o = c.o, d = c.d, inc = c.inc, col = c.col, rgb = c.inc;      // rgb = inc: as the callers enter it
+        uint32_t state = c.state;
+        int bounce = c.bounce;
+        const bool finished = pti::shade_hit<Quad>(TwinMats(), c.mat, c.normal, c.hitp, c.mode, c.max_bounce, o, d, inc, col, state, bounce, rgb);
+        r[0] = fw(o.x), r[1] = fw(o.y), r[2] = fw(o.z), r[3] = fw(d.x), r[4] = fw(d.y), r[5] = fw(d.z);
+        r[6] = fw(inc.x), r[7] = fw(inc.y), r[8] = fw(inc.z), r[9] = fw(col.x), r[10] = fw(col.y), r[11] = fw(col.z);
+        r[12] = state, r[13] = (uint32_t)bounce, r[14] = (uint32_t)finished;
+        r[15] = fw(rgb.x), r[16] = fw(rgb.y), r[17] = fw(rgb.z);
+    }
+    static void ref(const Case&, const Ctx&, const uint32_t* self, uint32_t* r) {
+        for (int i = 0; i < W; i++) r[i] = self[i];
+    }
+    static bool positive(const Case&, const uint32_t* r) { return r[14] != 0u; }   // the path ended
+    static void nudge(Case& c) { c.state ^= 1u; c.normal.x = step(c.normal.x); c.hitp.x = step(c.hitp.x); }
+    static void show(const Case& c) {
+        std::fprintf(stderr, "normal=(%a,%a,%a) hitp=(%a,%a,%a) o=(%a,%a,%a) d=(%a,%a,%a) inc=(%a,%a,%a) col=(%a,%a,%a) state=%08x bounce=%d max=%d mode=%d mat=%d",
+                     c.normal.x, c.normal.y, c.normal.z, c.hitp.x, c.hitp.y, c.hitp.z, c.o.x, c.o.y, c.o.z, c.d.x, c.d.y, c.d.z, c.inc.x,
+                     c.inc.y, c.inc.z, c.col.x, c.col.y, c.col.z, c.state, c.bounce, c.max_bounce, c.mode, c.mat);
+    }
+};
+
 // ------------------------------------------------------------------ the whole case set
 struct Cases {
     std::vector<isc::SlabCase> slab, slab_wild;
@@ -453,6 +597,12 @@ struct Cases {
     std::vector<twc::WideNextCase> wide_next;
     std::vector<twc::RngCase> rng;
     std::vector<twc::VecCase> vec;
+    std::vector<twc::GuardCase> guard;
+    std::vector<twc::SphereCase> sphere;
+    std::vector<twc::LeafChoiceCase> leaf_choice;
+    std::vector<twc::PinholeCase> pinhole;
+    std::vector<twc::SkyDepthCase> sky_depth;
+    std::vector<twc::BounceCase> bounce;
     long dropped = 0, aces_boundaries = 0;   // cases a generator left its domain with (asserted 0)
 };
 // `div`: every count divided by it (the CPU test runs a fraction of the set; the device twin all of it)
@@ -478,6 +628,12 @@ inline void generate(Cases& C, long div) {
     twc::wide_next_cases(cnt(twc::kWideNext), C.wide_next);
     twc::rng_cases(cnt(twc::kRng), C.rng);
     twc::vec_cases(cnt(twc::kVec), C.vec);
+    twc::guard_cases(cnt(twc::kGuard), C.guard);
+    twc::sphere_cases(cnt(twc::kSphere), C.sphere);
+    twc::leaf_choice_cases(cnt(twc::kLeafChoice), C.leaf_choice);
+    twc::pinhole_cases(cnt(twc::kPinhole), C.pinhole);
+    twc::sky_depth_cases(cnt(twc::kSkyDepth), C.sky_depth);
+    twc::bounce_cases(cnt(twc::kBounce), C.bounce);
 }
 inline SweepCtx sweep_ctx(const twc::SweepTable& T, const Quad* table, bool flip) {
     SweepCtx x;

@@ -65,6 +65,12 @@ int main(int argc, char** argv) {
     family<twf::WideNext>(C.wide_next);
     family<twf::Rng>(C.rng);
     family<twf::Vec>(C.vec);
+    family<twf::Guard>(C.guard);
+    family<twf::Sphere>(C.sphere);
+    family<twf::LeafChoice>(C.leaf_choice);
+    family<twf::Pinhole>(C.pinhole);
+    family<twf::SkyDepth>(C.sky_depth);
+    family<twf::Bounce>(C.bounce);
 
     // the lane mix __any exists for: groups of 64 consecutive wide_next cases with a flushing and a non-flushing step
     long mixed = 0, flushes = 0;

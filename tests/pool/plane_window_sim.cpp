@@ -104,7 +104,7 @@ int segment(f3 o, f3 d, int own, Acc& A, float* t_out, int* tri_out) {
     *t_out = ro.t;
     *tri_out = ro.tri;
     const int hit_leaf = hit_node < 0 ? -1 : (int)(std::find(chain.begin(), chain.end(), hit_node) - chain.begin());
-    if (!in_guard(o, d)) { slow++; return hit_leaf; }
+    if (!pti::ray_in_guard(true, o, d)) { slow++; return hit_leaf; }   // the kernel's own verdict
     // the kernel's segment set-up: the candidate mask, then the own pair's bit
     const f3 rd = mk(pt::rcp_fast(d.x), pt::rcp_fast(d.y), pt::rcp_fast(d.z));
     f3 ol, oh;

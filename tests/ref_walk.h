@@ -3,7 +3,8 @@
 // :309-365; hit_triangle :274-307), restated on pt_math.h's pinned operations.  An independent
 // restatement: nothing here may call pt_isect.h, pt_cull.h or pt_wide.h, the kernel-side code
 // the models check against it.
-// Used by tests/wide/wide_sim.cpp, tests/wide/cert_fuzz.cpp and tests/cull/window_cull_sim.cpp.
+// Used by tests/wide/wide_sim.cpp, tests/wide/cert_fuzz.cpp, tests/cull/window_cull_sim.cpp and the other walk
+// models, and by the device twin's families (tests/device/twin_families.h).
 #pragma once
 
 #include "../opengl-path-tracing_amd/csrc/pt_math.h"
@@ -92,14 +93,21 @@ inline float sphere_t(f3 o, f3 d) {   // :372-385 (the closest sphere hit in (1e
     return t;
 }
 
-// the leaf's 2-way choice (:411-428) at t; returns whether t moves
+// the leaf's 2-way choice (:411-428) between its triangles' hits at t: 1 the first, 2 the second, 0 neither
+// (the reference of the device twin's leaf_choice family, tests/device/twin_families.h)
+inline int choose(float h1, float h2, float t) {
+    if (h1 > 0.0001f && h1 < t && (h1 < h2 || h2 < 0.0001f)) return 1;
+    if (h2 > 0.0001f && h2 < t) return 2;
+    return 0;
+}
+// ... of leaf bnode; returns whether t moves
 inline bool leaf_choice(int bnode, f3 o, f3 d, float t, float& nt_, int& ntri) {
     const float* b = &nodes[12 * (size_t)bnode];
     const int t0 = (int)b[8], t1 = (int)b[9];
     const float h1 = hit_triangle(o, d, t0), h2 = hit_triangle(o, d, t1);
-    if (h1 > 0.0001f && h1 < t && (h1 < h2 || h2 < 0.0001f)) { nt_ = h1; ntri = t0; return true; }
-    if (h2 > 0.0001f && h2 < t) { nt_ = h2; ntri = t1; return true; }
-    return false;
+    const int c = choose(h1, h2, t);
+    if (c) { nt_ = c == 1 ? h1 : h2; ntri = c == 1 ? t0 : t1; }
+    return c != 0;
 }
 
 // The reference walk.  A model's own bookkeeping rides on two hooks: at_node(bi, hb, t) after
@@ -128,8 +136,9 @@ RefOut ref_walk(f3 o, f3 d, float t0, AtNode at_node, AtLeaf at_leaf) {
     return r;
 }
 
-// The exact-reciprocal guard, ray half.  (A restatement: the kernel's own is an
-// expression inside k_render_sm's segment set-up, pt_render_sm.h, on pt::in_guard / in_range_abs.)
+// The exact-reciprocal guard, ray half.  (A restatement in float compares: the kernel's own is
+// pti::ray_in_guard, pt_isect.h, on the bit-pattern windows pt::in_guard / in_range_abs; this one is the reference
+// of the device twin's guard family.)
 inline bool in_guard(f3 o, f3 d) {
     auto g0 = [](float v) { float a = std::fabs(v); return v == 0.0f || (a >= 0x1p-40f && a <= 0x1p60f); };
     auto g1 = [](float v) { float a = std::fabs(v); return a >= 0x1p-20f && a <= 2.0f; };

@@ -28,7 +28,9 @@ HIPCC = "/opt/rocm/bin/hipcc"
 # family: (cases, positives, boolean, has an independent reference) -- the host reference's counts at the
 # default case set.  positives: slab / slab_wild / cull accept, sweep mask not empty, tri hit_triangle hits, aces
 # not black, accumulate on, quantise below the cap of 64, target q above target_q, retire true, fold S1 > 1,
-# wide_hits any child pending, wide_next flushes, rng normal > 0, vec dot(a, a) inside the fast forms' guard.
+# wide_hits any child pending, wide_next flushes, rng normal > 0, vec dot(a, a) inside the fast forms' guard,
+# guard inside, sphere distance above 1e-4, leaf_choice takes a triangle, pinhole right of the centre column,
+# sky_depth with the sky on, bounce ends the path.
 EXPECTED = {
     "slab": (2000003, 736846, True, True),
     "slab_wild": (500009, 163818, True, False),
@@ -45,6 +47,12 @@ EXPECTED = {
     "wide_next": (1000003, 13170, False, False),
     "math_rng": (1048579, 523977, False, False),
     "math_vec": (500009, 283099, False, False),
+    "guard": (100003, 43975, True, True),
+    "sphere": (100003, 52813, True, True),
+    "leaf_choice": (100003, 39281, True, True),
+    "pinhole": (100003, 54958, False, True),
+    "sky_depth": (100003, 87641, False, False),
+    "bounce": (100003, 91441, False, False),
 }
 
 
@@ -109,7 +117,9 @@ def test_no_case_is_dropped(result):
 def test_host_compilation_equals_the_reference(result, name):
     """slab_fast / slab_oct against the IEEE chain, slab_oct_cons against sweep_hit, sweep_mask against the mask of
     sweep_hit verdicts, the triangle tests and the tonemap against the oracle, the running mean, quantise and the
-    moment fold against their double-rounded definitions.  (Families without a reference report 0 by construction.)"""
+    moment fold against their double-rounded definitions, the guard and the leaf's choice against the float compares
+    of tests/ref_walk.h, the sphere distance against the oracle's hit_sphere, the film coordinates against the
+    reference's division.  (Families without a reference report 0 by construction.)"""
     assert result["families"][name]["host_vs_ref"] == 0, result["stderr"]
     assert result["rc"] == 0
 

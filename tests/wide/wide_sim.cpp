@@ -111,7 +111,7 @@ void segment(f3 o, f3 d, Acc& A, float* t_out, int* tri_out) {
     A.rv += ro.nodes;
     A.rl += ro.leaves;
     A.ref_top += top;
-    if (!in_guard(o, d)) { slow++; return; }
+    if (!pti::ray_in_guard(true, o, d)) { slow++; return; }   // the kernel's own verdict
     const WideOut wo = wide_walk(o, d, t0);
     uint32_t a, b;
     std::memcpy(&a, &ro.t, 4);
